@@ -22,7 +22,22 @@ roofline.frac_end_to_end uses the whole step time; roofline.traffic is the
 dominant kernel's HBM bytes per launch from the committed rocprofv3 PMC
 passes (profiles/pmc_r06.json) and traffic_ratio = traffic / algorithmic.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+A plain run does only what the headline figure needs: set up, warm up, time
+--steps steps, write the outputs if --dump-outputs is given, print the result
+line.  Everything else the bench measures (per-kernel times and the roofline
+object, the config-3 decode, the stats fit, configs 2 / 4 / 5, the LFQ
+projections, the model, the CPU baselines) runs under --full only, after the
+timed steps; the --no-* options switch single legs of a --full run off.
+
+--dump-outputs DIR writes what the last timed step returned (BatchEncoder's
+packed rows) as DIR/<name>.npy, float32 / float64: the rows of a fixed seeded
+sample of DUMP_ROWS packed rows (codes, positions, channels, image_ids,
+key_pad_mask, and sample_rows = which rows) plus, over every row, the per-row
+sums of the codes and of the unpadded tokens.  The inputs are the counter RNG's
+and the committed PatchNorm tables, so two runs with the same arguments see
+identical inputs.  Rank r > 0 of a multi-GPU run writes <name>.rank<r>.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -43,6 +58,8 @@ HBM_ACHIEVABLE_GBS = 6290.0  # MI355X_MICROARCH.md: 6.29 TB/s measured (float4 c
 FP32_MFMA_PEAK_TF = 157.3    # dense fp32 MFMA (= vector) peak
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_r06.json")
 CPU_CAL_FILE = os.path.join(ROOT, "profiles", "cpu_calibration_r02.json")
+DUMP_ROWS = 128              # packed rows of --dump-outputs' sample (1024 x 512^2: about 30 MB in all)
+DUMP_SEED = 20240607
 
 
 def launcher_command(argv, gpus, port=None):
@@ -398,6 +415,24 @@ def config5_leg(enc, dev, rank, world, dist, shard):
             "value": round(imgs * H * H / encs / 1e6, 1), "unit": "Mpix/s (encode time, max over ranks)"}
 
 
+def dump_outputs(out, directory, rank):
+    """--dump-outputs: the packed rows the timed path returned, as float32 /
+    float64 .npy files (every value is an integer below 2^24 or a bool, so
+    float32 holds it exactly)."""
+    os.makedirs(directory, exist_ok=True)
+    suffix = f".rank{rank}" if rank else ""
+    n_rows = out["codes"].shape[0]
+    rows = np.sort(np.random.default_rng(DUMP_SEED).permutation(n_rows)[:DUMP_ROWS])
+    sel = torch.from_numpy(rows).to(out["codes"].device)
+    arrays = {k: out[k][sel].to(torch.float32).cpu().numpy()
+              for k in ("codes", "positions", "channels", "image_ids", "key_pad_mask")}
+    arrays["sample_rows"] = rows.astype(np.float64)
+    arrays["codes_row_sum"] = out["codes"].sum(dim=(1, 2)).to(torch.float64).cpu().numpy()
+    arrays["tokens_per_row"] = (~out["key_pad_mask"]).sum(dim=1).to(torch.float64).cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a)
+
+
 def kernel_times(ctx, fn, n):
     """Per-kernel device times of n calls of fn (HIP events around each launch
     on its own stream, dctae_set_timing), outside any timed region."""
@@ -425,6 +460,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024, help="images per GPU per step")
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: kernel times / roofline, decode, stats fit, "
+                         "configs 2 / 4 / 5, LFQ projections, CPU baselines (and the model with --model)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
@@ -489,18 +529,22 @@ def main():
         enc(x)
     torch.cuda.synchronize(dev)
 
-    timing = not args.no_kernel_timing
+    full = args.full   # every leg but the timed steps below runs under --full only
+    timing = full and not args.no_kernel_timing
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        enc(x)
+        out = enc(x)
     torch.cuda.synchronize(dev)
     if dist:
         dist.barrier()
     el = time.perf_counter() - t0
     ops.check_device_errors(dev)
+    if args.dump_outputs and out is not None:
+        dump_outputs(out, args.dump_outputs, rank)
     if timing:
         # per-kernel device times (HIP events around each launch, on its stream) in a
         # separate pass: the event records stay out of the timed region above
@@ -583,7 +627,7 @@ def main():
 
     # config 3: decode of this step's codes back to RGB, timed the same way
     decode = None
-    if not args.no_decode:
+    if full and not args.no_decode:
         try:
             dec = fe_mod.BatchDecoder(enc, pn, lfq)
             packed = enc(x)
@@ -631,20 +675,20 @@ def main():
             decode = {"error": f"{type(e).__name__}: {e}"}
 
     stats = None
-    if not args.no_stats:
+    if full and not args.no_stats:
         try:
             stats = stats_fit_leg(pkg, fe, dev, rank, world, dist, args.steps)
         except Exception as e:  # noqa: BLE001 — the encode line must still print
             stats = {"error": f"{type(e).__name__}: {e}"}
 
     configs = None
-    if not args.no_configs:
+    if full and not args.no_configs:
         try:
             configs = config_legs(pkg, fe, pn, lfq, dev, rank, args.steps)
         except Exception as e:  # noqa: BLE001 — the encode line must still print
             configs = {"error": f"{type(e).__name__}: {e}"}
 
-    if args.config5_shard > 0 and B == 1024 and H == 512:
+    if full and args.config5_shard > 0 and B == 1024 and H == 512:
         try:
             c5 = config5_leg(enc, dev, rank, world, dist, args.config5_shard)
         except Exception as e:  # noqa: BLE001 — the encode line must still print
@@ -654,7 +698,7 @@ def main():
 
     # the DCTAutoencoder transformer forward (patch14-l, 4 rows x 3072 tokens)
     model = None
-    if args.model and not args.no_model:
+    if full and args.model and not args.no_model:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import model_bench
@@ -663,7 +707,7 @@ def main():
             model = {"error": f"{type(e).__name__}: {e}"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import ref_cpu
         threads = min(16, os.cpu_count() or 1)
         tables = ref_cpu.NormTables(torch.from_numpy(tabs["n"]), torch.from_numpy(tabs["median"]),
@@ -691,6 +735,7 @@ def main():
                                                   if world > 1 else None)},
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": full,
             "ms_per_step": round(ms_step, 4),
             "higher_is_better": True,
             "scaling": "weak",

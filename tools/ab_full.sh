@@ -11,11 +11,12 @@ for lib in "$@"; do
   n=$((n+1))
   unset DCTAE_LIBRARY
   [ "$lib" != default ] && export DCTAE_LIBRARY=$lib
-  timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-stats > gpurun_out/ab_full_$n.log 2>&1
+  log=$(mktemp)
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-stats > "$log" 2>&1
   rc=$?
   echo "=== [$lib] rc=$rc"
-  if [ $rc -ne 0 ]; then tail -20 gpurun_out/ab_full_$n.log; exit $rc; fi
-  grep '^{' gpurun_out/ab_full_$n.log | python -c "
+  if [ $rc -ne 0 ]; then tail -20 "$log"; exit $rc; fi
+  grep '^{' "$log" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 oc=d.get('other_configs') or {}

@@ -12,7 +12,7 @@ for spec in "$@"; do
   args=""
   for o in $opts; do args="$args --opt $o"; done
   if [ "$lib" = "-" ]; then unset DCTAE_LIBRARY; else export DCTAE_LIBRARY="$lib"; fi
-  timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-decode --no-stats \
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-decode --no-stats \
       --no-configs --no-model $args > gpurun_out/ab_bench.log 2>&1
   rc=$?
   echo "=== [$spec] rc=$rc"

@@ -13,7 +13,7 @@ for spec in "$@"; do
   args=""
   for o in $opts; do args="$args --opt $o"; done
   if [ "$lib" = "-" ]; then unset DCTAE_LIBRARY; else export DCTAE_LIBRARY="$lib"; fi
-  timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-stats \
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-stats \
       --no-configs --no-model $args > gpurun_out/ab2_bench.log 2>&1
   rc=$?
   echo "=== [$spec] rc=$rc"

@@ -12,7 +12,7 @@ if [ $rc -ne 0 ]; then tail -40 gpurun_out/dec_tests.log; exit $rc; fi
 for opts in "$@"; do
   args=""
   for o in $opts; do args="$args --opt $o"; done
-  timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-stats --no-configs \
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-stats --no-configs \
       $args > gpurun_out/dec_bench.log 2>&1
   rc=$?
   echo "=== [$opts] rc=$rc"

@@ -10,10 +10,10 @@ export TMPDIR=/tmp
 TAG=${TAG:-r05}
 OUT=gpurun_out/evidence
 rm -rf $OUT; mkdir -p $OUT
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_$TAG.log 2>&1 || { tail -20 $OUT/bench_$TAG.log; exit 1; }
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_$TAG.log 2>&1 || { tail -20 $OUT/bench_$TAG.log; exit 1; }
 tail -c 300 $OUT/bench_$TAG.log; echo
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- \
-    python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timing --no-stats --no-configs \
+    python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timing --no-stats --no-configs \
     > $OUT/rocprof_$TAG.log 2>&1 || { tail -20 $OUT/rocprof_$TAG.log; exit 1; }
 find $OUT/prof -name "*kernel_stats.csv" -exec cp {} $OUT/rocprof_kernel_stats_$TAG.csv \;
 cut -d, -f1-4 $OUT/rocprof_kernel_stats_$TAG.csv | head -14

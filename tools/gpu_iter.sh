@@ -15,7 +15,7 @@ if [ $rc -ne 0 ]; then tail -40 gpurun_out/iter_tests.log; exit $rc; fi
 for opts in "$@"; do
   args=""
   for o in $opts; do args="$args --opt $o"; done
-  timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-decode --no-stats \
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-decode --no-stats \
       --no-configs --no-model $args > gpurun_out/iter_bench.log 2>&1
   rc=$?
   echo "=== [$opts] rc=$rc"
@@ -24,7 +24,7 @@ for opts in "$@"; do
 done
 if [ -n "${PROF:-}" ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/iprof -o run --output-format csv -- \
-      python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-decode --no-stats --no-configs \
+      python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-decode --no-stats --no-configs \
       --no-model > gpurun_out/iprof.log 2>&1 || { tail -20 gpurun_out/iprof.log; exit 1; }
   find gpurun_out/iprof -name "*kernel_stats.csv" -exec cat {} \; | cut -d, -f1-8 | head -20
 fi

@@ -9,7 +9,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-DCTAE_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --gpus ${RANKS:-2} --steps 5 --warmup 2 --no-cpu-baseline \
+DCTAE_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --full --gpus ${RANKS:-2} --steps 5 --warmup 2 --no-cpu-baseline \
     --no-configs --no-model > gpurun_out/multirank.log 2>&1
 rc=$?; tail -c 1500 gpurun_out/multirank.log; echo
 [ $rc -ne 0 ] && exit $rc

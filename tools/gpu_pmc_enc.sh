@@ -8,7 +8,7 @@ OUT=${PMC_OUT:-gpurun_out/pmc_enc}
 rm -rf $OUT; mkdir -p $OUT
 # DECODE=1: the config-3 decode leg runs too (its kernels land in the same passes)
 DEC="--no-decode"; [ -n "${DECODE:-}" ] && DEC=""
-BENCH="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-stats --no-model --no-configs $DEC ${BENCH_ARGS:-}"
+BENCH="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-stats --no-model --no-configs $DEC ${BENCH_ARGS:-}"
 # CMD=...: profile another program instead (e.g. CMD="python3 tools/cfg4_run.py 1")
 BENCH=${CMD:-$BENCH}
 i=0

@@ -7,10 +7,11 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 TAG=${TAG:-r02}
 mkdir -p gpurun_out/evidence
-timeout -k 10 900 python bench.py > gpurun_out/evidence/bench_$TAG.log 2>&1 || { tail -20 gpurun_out/evidence/bench_$TAG.log; exit 1; }
-tail -c 600 gpurun_out/evidence/bench_$TAG.log
+BENCH_LOG=${BENCH_LOG:-$(mktemp)}   # the bench's log (BENCH_LOG=path keeps it)
+timeout -k 10 900 python bench.py --full > "$BENCH_LOG" 2>&1 || { tail -20 "$BENCH_LOG"; exit 1; }
+tail -c 600 "$BENCH_LOG"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/evidence/prof -o run --output-format csv -- \
-    python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timing --no-stats --no-configs \
+    python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timing --no-stats --no-configs \
     > gpurun_out/evidence/rocprof_$TAG.log 2>&1 || { tail -20 gpurun_out/evidence/rocprof_$TAG.log; exit 1; }
 find gpurun_out/evidence/prof -name "*kernel_stats.csv" -exec cp {} gpurun_out/evidence/rocprof_kernel_stats_$TAG.csv \;
 cut -d, -f1-4 gpurun_out/evidence/rocprof_kernel_stats_$TAG.csv | head -12

@@ -38,7 +38,7 @@ for opts in "$@"; do
     continue
   fi
   dec="--no-decode"; [ -n "${DEC:-}" ] && dec=""
-  timeout -k 10 300 python bench.py --steps ${STEPS:-30} --warmup 3 --no-cpu-baseline $dec --no-stats \
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-30} --warmup 3 --no-cpu-baseline $dec --no-stats \
       --no-configs --no-model $args > gpurun_out/try_bench.log 2>&1
   rc=$?
   echo "=== [$opts] rc=$rc"

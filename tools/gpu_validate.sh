@@ -12,6 +12,7 @@ if [ $rc -ne 0 ]; then grep -E "Error|assert|FAILED" gpurun_out/val_tests.log | 
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/val_smoke.log 2>&1 || { tail -30 gpurun_out/val_smoke.log; exit 1; }
 tail -2 gpurun_out/val_smoke.log
 if [ -z "${NO_BENCH:-}" ]; then
-  timeout -k 10 600 python bench.py > gpurun_out/val_bench.log 2>&1 || { tail -30 gpurun_out/val_bench.log; exit 1; }
-  grep '^{' gpurun_out/val_bench.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], json.dumps(d['roofline']), json.dumps({k:v['avg_ms'] for k,v in d['kernels'].items()}), json.dumps(d.get('other_configs')), json.dumps({k: d['decode'].get(k) for k in ('value','ms_per_step','hbm_roofline_frac')}))"
+  BENCH_LOG=${BENCH_LOG:-$(mktemp)}   # the bench's log (BENCH_LOG=path keeps it)
+  timeout -k 10 600 python bench.py --full > "$BENCH_LOG" 2>&1 || { tail -30 "$BENCH_LOG"; exit 1; }
+  grep '^{' "$BENCH_LOG" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], json.dumps(d['roofline']), json.dumps({k:v['avg_ms'] for k,v in d['kernels'].items()}), json.dumps(d.get('other_configs')), json.dumps({k: d['decode'].get(k) for k in ('value','ms_per_step','hbm_roofline_frac')}))"
 fi

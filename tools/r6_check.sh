@@ -16,5 +16,6 @@ rc=$?
 echo "tests rc=$rc $(tail -1 gpurun_out/chk_tests.log)"; grep "^FAILED" gpurun_out/chk_tests.log | head
 [ $rc -gt 1 ] && exit $rc
 [ -n "$NOBENCH" ] && exit 0
-timeout -k 10 600 python -u bench.py > gpurun_out/chk_bench.log 2>&1 || exit 13
-tail -1 gpurun_out/chk_bench.log | cut -c1-600
+BENCH_LOG=${BENCH_LOG:-$(mktemp)}   # the bench's log (BENCH_LOG=path keeps it)
+timeout -k 10 600 python -u bench.py --full > "$BENCH_LOG" 2>&1 || exit 13
+tail -1 "$BENCH_LOG" | cut -c1-600
