@@ -243,9 +243,7 @@ void default_colors(ColorMats& cm) {
 // the call-ordering event (order_after_previous / mark_done) only orders this
 // context's calls across streams of one device: no system-scope fence (its
 // cache write-back sat between back-to-back calls)
-#ifndef DCTAE_DONE_EVT_FLAGS
-#define DCTAE_DONE_EVT_FLAGS (hipEventDisableTiming | hipEventDisableSystemFence)
-#endif
+constexpr unsigned kDoneEvtFlags = hipEventDisableTiming | hipEventDisableSystemFence;
 
 struct Timer {
   dctae_ctx* ctx;
@@ -503,9 +501,6 @@ GemmProblem gemm(const float* A, int64_t sAc, int64_t sAm, int64_t sAk, const fl
 // of once per XCD.  Groups go to the least-loaded XCD; the lanes are padded to
 // equal length with empty tiles (problem -1, the kernels return at once) so
 // the b % 8 affinity holds to the end of the launch.
-#ifndef DCTAE_DEAL_PROBLEM
-#define DCTAE_DEAL_PROBLEM 1
-#endif
 void xcd_deal_tiles(std::vector<TileRef>& t, const GemmProblem* probs, int share) {
   if (t.size() < 16 || share == 0) return;
   // with many problems (>= 64, e.g. a batch of images), all tiles of a problem
@@ -520,7 +515,7 @@ void xcd_deal_tiles(std::vector<TileRef>& t, const GemmProblem* probs, int share
     std::sort(seen.begin(), seen.end());
     n_prob = (int)(std::unique(seen.begin(), seen.end()) - seen.begin());
   }
-  const bool per_problem = DCTAE_DEAL_PROBLEM && n_prob >= 64;
+  const bool per_problem = n_prob >= 64;
   std::vector<std::vector<TileRef>> groups;
   std::map<std::pair<int, int>, size_t> gi;
   for (const TileRef& r : t) {
@@ -881,7 +876,7 @@ int dctae_ctx_create(int device, dctae_ctx** out) {
   c->device = device;
   default_colors(c->cm);
   if (hipEventCreateWithFlags(&c->plan_evt, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->done_evt, DCTAE_DONE_EVT_FLAGS) != hipSuccess ||
+      hipEventCreateWithFlags(&c->done_evt, kDoneEvtFlags) != hipSuccess ||
       hipMalloc((void**)&c->err_dev, sizeof(int)) != hipSuccess || hipMemset(c->err_dev, 0, sizeof(int)) != hipSuccess) {
     g_err = "context allocation failed";
     delete c;

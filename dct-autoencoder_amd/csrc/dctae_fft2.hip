@@ -9,17 +9,6 @@
 #include "dctae_launch.h"
 #include "dctae_spec512.h"
 
-// config 2's T with the nontemporal hint: on for k_rows224p's stores (rows
-// 0.060 -> 0.057 ms), off for k_cols224's loads (their strided 8-byte reads
-// share lines through L2: cols 0.052 -> 0.069 ms with it), same-box A/B r05.
-#ifndef DCTAE_T224_ST_NT
-#define DCTAE_T224_ST_NT 1
-#endif
-#ifndef DCTAE_T224_LD_NT
-#define DCTAE_T224_LD_NT 0
-#endif
-
-
 namespace dctae {
 
 // padded complex slot of element m: one spare slot every 16 keeps the
@@ -47,10 +36,7 @@ __device__ __forceinline__ void rows2_item(const ImgDesc& d, int y_first, const 
   constexpr int B1 = M / R1, B2 = M / R2;
   constexpr int PX = (N + 63) / 64;        // pixels per lane and row
   constexpr int KI = (M + 63) / 64;        // k = lane + 64 i, i < KI, covers k < M (k = M by lane 0)
-#ifndef DCTAE_RPW224
-#define DCTAE_RPW224 1   // 224-wide rows: one row per wave (0.074 vs 0.081 ms at 4 rows per wave, config 2)
-#endif
-  constexpr int RPW = N == 224 ? DCTAE_RPW224 : 4;   // rows per wave (block = 4 RPW rows)
+  constexpr int RPW = 4;                   // rows per wave (block = 4 RPW rows)
   static_assert(R1 * R2 == M, "two-pass plan");
   static_assert(3 * B1 <= 64 && 3 * B2 <= 64, "one butterfly per lane per pass");
   static_assert(R1 == 16, "first radix 16 (Ns of pass 2 = 16)");
@@ -183,7 +169,8 @@ __global__ __launch_bounds__(256) void k_fft_rows2(const ImgDesc* __restrict__ i
 
 // ---------------------------------------------------------------------------
 // k_rows224p<RW>: the row pass of 224-wide images (config 2) with RW = 2 or 3
-// rows per wave (3 RW channel-rows) instead of rows2_item's one: pass 1 (radix
+// rows per wave (3 RW channel-rows) instead of one (the removed
+// k_fft_rows2<224, 16, 7>: 0.074 ms on config 2, 0.081 at 4 rows per wave): pass 1 (radix
 // 16, 7 butterflies per channel-row) fills 42 / 63 of 64 lanes instead of 21,
 // a wave's RW contiguous rows are 7 / 10.5 pixels per lane instead of 3.5 of 4,
 // the colour mix runs on pixel pairs (v_pk_fma_f32, splat_mix) and the Makhoul
@@ -340,13 +327,9 @@ __global__ __launch_bounds__(256) void k_rows224p(const ImgDesc* __restrict__ im
         const float4 cc = pc[k];
         const float2 A = z[cr][pad16(k)], P = z[cr][pad16(k == 0 ? 0 : M - k)];
         const cf t = makhoul_pair((cf){A.x, A.y}, (cf){P.x, P.y}, (cf){cc.x, cc.y}, (cf){cc.z, cc.w});
-#if DCTAE_T224_ST_NT
+        // nontemporal: rows 0.060 -> 0.057 ms (config 2, same-box A/B r05)
         if (oa[i] >= 0) __builtin_nontemporal_store(t.x, tb + oa[i]);
         if (ob[i] >= 0) __builtin_nontemporal_store(t.y, tb + ob[i]);
-#else
-        if (oa[i] >= 0) tb[oa[i]] = t.x;
-        if (ob[i] >= 0) tb[ob[i]] = t.y;
-#endif
       }
     }
     if (lane == 0 && M < Kw) {   // k = M: Z[0] with itself
@@ -656,20 +639,11 @@ __global__ __launch_bounds__(256) void k_fft_cols7(const ImgDesc* __restrict__ i
 // items (neighbouring strips share L2 lines; their threshold tables stay in
 // that XCD's L2), the next image's T' loads in flight during the transform.
 // Images per block, same-box A/B (1024 x 512^2, NT T', round 5): 2 -> 0.588-
-// 0.590 ms, 3 -> 0.570-0.571 (default: a block's first image, whose loads
+// 0.590 ms, 3 -> 0.570-0.571 (chosen: a block's first image, whose loads
 // nothing hides, is a third of its work instead of half), 4 -> 0.581, 6 ->
 // 0.575-0.577, 8 -> 0.579-0.580.
-#ifndef DCTAE_C5B_IPB
-#define DCTAE_C5B_IPB 3
-#endif
-// PatchNorm-output columns (cols512b_norm_epilogue): 1 = on, 0 = the generic
-// token epilogue; images per block
-#ifndef DCTAE_C5B_NORM
-#define DCTAE_C5B_NORM 1
-#endif
-#ifndef DCTAE_C5B_NORM_IPB
-#define DCTAE_C5B_NORM_IPB 3
-#endif
+constexpr int kC5bIpb = 3;
+constexpr int kC5bNormIpb = 3;   // images per block of the PatchNorm-output columns (cols512b_norm_epilogue)
 template <bool THR, int IPB, bool NORM = false>
 __global__ __launch_bounds__(256) void k_cols512b(const ImgDesc* __restrict__ imgs, const int* __restrict__ list,
                                                   int n_list, const float* __restrict__ ws,
@@ -701,7 +675,7 @@ __global__ __launch_bounds__(256) void k_cols512b(const ImgDesc* __restrict__ im
   }
   float2 tn[NORM ? 2 : 1][14];
   if constexpr (NORM) cols_norm_tables(c, strip, ep, tn);
-  TPiece qa[8];
+  float4 qa[8];
   cols512b_load(c, strip, ws + imgs[list[k0]].ws_t, qa);
   __syncthreads();   // tables
 #pragma unroll
@@ -717,7 +691,7 @@ __global__ __launch_bounds__(256) void k_cols512b(const ImgDesc* __restrict__ im
       // the next image's loads in flight during this one; unconditional (the
       // last image of the list reloads itself): a conditional load makes the
       // compiler merge qn / qa with register copies right behind the loads
-      TPiece qn[8];
+      float4 qn[8];
       if (u + 1 < IPB) cols512b_load(c, strip, ws + imgs[list[min(k + 1, n_list - 1)]].ws_t, qn);
       float4 qf[8];
       t_decode(qa, qf);
@@ -751,7 +725,7 @@ struct Cols512wLds {
   float4 pc[256];
 };                              // 70,656 B: 2 blocks per CU
 
-__device__ __forceinline__ void cols512w_load(int c, int kx, const float* __restrict__ T, TPiece (&q)[8]) {
+__device__ __forceinline__ void cols512w_load(int c, int kx, const float* __restrict__ T, float4 (&q)[8]) {
   t_load_column(c, kx, opaque_tid() & 15, T, q);
 }
 
@@ -875,7 +849,7 @@ __global__ __launch_bounds__(448) __attribute__((amdgpu_waves_per_eu(4))) void k
     const int G = opaque_tid() >> 4, sg = G >= KS ? 1 : 0;
     return KS * (2 * sp + sg) + G - KS * sg;
   }();
-  TPiece qa[8];
+  float4 qa[8];
   cols512w_load(c, kx, ws + imgs[list[k0]].ws_t, qa);
   __syncthreads();   // tables
 #pragma unroll
@@ -883,7 +857,7 @@ __global__ __launch_bounds__(448) __attribute__((amdgpu_waves_per_eu(4))) void k
     const int k = k0 + u;
     if (k >= n_list) break;   // block-uniform
     t_opaque(qa);
-    TPiece qn[8];
+    float4 qn[8];
     if (u + 1 < IPB) cols512w_load(c, kx, ws + imgs[list[min(k + 1, n_list - 1)]].ws_t, qn);
     // the previous image's scores (its rmax was written before the barrier that ended it)
     if (u > 0) cols512w_scores(L, imgs[list[k - 1]], c, sp, ep, sk);
@@ -907,21 +881,21 @@ void launch_cols512b(const ImgDesc* imgs, const int* list, int n_list, const flo
   const bool thr = ep.median && ep.thr && !sk.norm && ep.maxph <= 32 && ep.cb_dim == 14 && ep.ncb == 14;
   // PatchNorm output (LFQ projections' staging, returned patches) with the
   // tables held per block: no raw copy, codes (if any) one codebook per tile row
-  const bool norm = DCTAE_C5B_NORM && !thr && sk.norm && ep.median && !sk.raw && ep.maxph == 32 && ep.maxpw == 32 &&
+  const bool norm = !thr && sk.norm && ep.median && !sk.raw && ep.maxph == 32 && ep.maxpw == 32 &&
                     (!sk.codes || (ep.cb_dim == 14 && ep.ncb == 14));
-  const int ipb = thr ? DCTAE_C5B_IPB : norm ? DCTAE_C5B_NORM_IPB : 2;
+  const int ipb = thr ? kC5bIpb : norm ? kC5bNormIpb : 2;
   const int grid = 96 * ((n_list + ipb - 1) / ipb);
   if (thr && wide) {   // two strips per 7-wave block: 48 items
-    hipLaunchKernelGGL((k_cols512w<DCTAE_C5B_IPB>), dim3(48 * ((n_list + DCTAE_C5B_IPB - 1) / DCTAE_C5B_IPB)), dim3(448),
-                       0, s, imgs, list, n_list, ws, tw, post, ep, sk);
+    hipLaunchKernelGGL((k_cols512w<kC5bIpb>), dim3(48 * ((n_list + kC5bIpb - 1) / kC5bIpb)), dim3(448), 0, s, imgs,
+                       list, n_list, ws, tw, post, ep, sk);
     return;
   }
   if (thr)
-    hipLaunchKernelGGL((k_cols512b<true, DCTAE_C5B_IPB>), dim3(grid), dim3(256), 0, s, imgs, list, n_list, ws, tw,
-                       post, ep, sk);
+    hipLaunchKernelGGL((k_cols512b<true, kC5bIpb>), dim3(grid), dim3(256), 0, s, imgs, list, n_list, ws, tw, post, ep,
+                       sk);
   else if (norm)
-    hipLaunchKernelGGL((k_cols512b<false, DCTAE_C5B_NORM_IPB, true>), dim3(grid), dim3(256), 0, s, imgs, list, n_list,
-                       ws, tw, post, ep, sk);
+    hipLaunchKernelGGL((k_cols512b<false, kC5bNormIpb, true>), dim3(grid), dim3(256), 0, s, imgs, list, n_list, ws, tw,
+                       post, ep, sk);
   else
     hipLaunchKernelGGL((k_cols512b<false, 2>), dim3(grid), dim3(256), 0, s, imgs, list, n_list, ws, tw, post, ep, sk);
 }
@@ -950,8 +924,8 @@ __global__ __launch_bounds__(256) void k_fft_cols4(const ImgDesc* __restrict__ i
 // ---------------------------------------------------------------------------
 // k_cols224: the column pass of 224-high images (config 2), two column items
 // (image, channel, tile-column strip) per block and 8 lanes per column instead
-// of k_fft_cols4's 16.  k_fft_cols4<224> is VALU-issue bound (666 VALU per
-// wave for 3.5 columns, 1 block per item); here, per wave of 7 columns:
+// of k_fft_cols4's 16.  The removed k_fft_cols4<224> was VALU-issue bound (666
+// VALU per wave for 3.5 columns, 1 block per item); here, per wave of 7 columns:
 //  * pass 1 (radix 16, 7 butterflies per column) runs on 7 / 8 of the lanes
 //    instead of 7 / 16; pass 2 (radix 7, 16 butterflies) is two per lane;
 //  * the Makhoul post is makhoul_pair2 on the (c1, c2, c3, c4) coefficients
@@ -969,14 +943,11 @@ __global__ __launch_bounds__(256) void k_cols224(const ImgDesc* __restrict__ img
                                                  EncParams ep, TokenSinks sk) {
 #pragma clang fp contract(fast)
   constexpr int N = 224, M = 112, R1 = 16, R2 = 7, B1 = 7, KS = 14;
-#ifndef DCTAE_C224_KSP
-#define DCTAE_C224_KSP 30
-#endif
   // LDS row stride (28 columns + pad): ds_read/write_b32 bank = dword mod 32 per
   // 32-lane half (4 columns x 8 lanes jj): pass 2 and the post step jj by 2 KSP
   // and pass 1's stores by 34 KSP, conflict-free when those are 4 x odd mod 32,
   // i.e. KSP = 2 mod 4 (30); 29 made them 2-way (PMC: 0.36 conflict share)
-  constexpr int KSP = DCTAE_C224_KSP;
+  constexpr int KSP = 30;
   static_assert(KSP >= 2 * KS, "28 columns");
   constexpr int ZROWS = 2 * (pad16(M - 1) + 1);   // padded complex layout, in floats per column
   static_assert(N <= ZROWS, "natural rows fit the complex layout");
@@ -1021,14 +992,10 @@ __global__ __launch_bounds__(256) void k_cols224(const ImgDesc* __restrict__ img
     const c4f2* src = reinterpret_cast<const c4f2*>(ws + tbase + ((int64_t)c * H + y0) * Kw + strip * KS) + p;
     const int64_t rstep = (int64_t)8 * Kw;   // 16 rows, in float2
     c4f2 tv[N / 16];
+    // (default cache policy: these strided 8-byte reads share lines through
+    // L2 -- nontemporal cols 0.052 -> 0.069 ms, same-box A/B r05)
 #pragma unroll
-    for (int k = 0; k < N / 16; ++k) {
-#if DCTAE_T224_LD_NT
-      tv[k] = __builtin_nontemporal_load(src + k * rstep);
-#else
-      tv[k] = src[k * rstep];
-#endif
-    }
+    for (int k = 0; k < N / 16; ++k) tv[k] = src[k * rstep];
     float* dst = zs + y0 * KSP + KS * u + 2 * p;
 #pragma unroll
     for (int k = 0; k < N / 16; ++k) {
@@ -1228,28 +1195,21 @@ int fft_spec_id(int N, const int* radix, int npass, int P) {
   return 0;
 }
 
-#ifndef DCTAE_ROWS224P
-#define DCTAE_ROWS224P 2   // rows per wave of k_rows224p (2 or 3; 0: k_fft_rows2<224>)
-#endif
-int fft_spec_rows_per_block(int spec) {
-  return spec == 2 ? (DCTAE_ROWS224P ? 4 * DCTAE_ROWS224P : 4 * DCTAE_RPW224) : (spec ? 16 : 0);
-}
+constexpr int kRows224pRW = 2;   // rows per wave of k_rows224p (2 or 3)
+int fft_spec_rows_per_block(int spec) { return spec == 2 ? 4 * kRows224pRW : (spec ? 16 : 0); }
 
 void launch_fft_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* rgb, float* ws,
                           const float2* tw, const float2* post, const ColorMats& cm, hipStream_t s) {
   if (n_blocks <= 0) return;
   if (spec == 1)
     hipLaunchKernelGGL((k_fft_rows2<512, 16, 16>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb, ws, tw, post, cm);
-  else if (spec == 2 && DCTAE_ROWS224P)
-    hipLaunchKernelGGL((k_rows224p<DCTAE_ROWS224P == 3 ? 3 : 2>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb,
-                       ws, tw, post, cm);
   else if (spec == 2)
-    hipLaunchKernelGGL((k_fft_rows2<224, 16, 7>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb, ws, tw, post, cm);
+    hipLaunchKernelGGL((k_rows224p<kRows224pRW>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb, ws, tw, post, cm);
 }
 
 // spec 1 (N = 512): k_fft_cols7 over `list` (the job's 512-high images, one
 // tile-column count qw) when given, else one k_fft_cols4 block per item;
-// spec 2 (N = 224): k_fft_cols4.  thr: codes-only encode on the exact LFQ
+// spec 2 (N = 224): k_cols224.  thr: codes-only encode on the exact LFQ
 // thresholds (14 x 14 codes), else the generic token epilogue.
 void launch_fft_cols_spec(int spec, const ImgDesc* imgs, const int4* blocks, int n_blocks, const float* ws,
                           const float2* tw, const float2* post, const EncParams& ep, const TokenSinks& sk,
@@ -1258,34 +1218,28 @@ void launch_fft_cols_spec(int spec, const ImgDesc* imgs, const int4* blocks, int
   const bool thr = ep.median && ep.thr && !sk.norm && ep.maxph <= 32 && ep.cb_dim == 14 && ep.ncb == 14;
   if (spec == 1 && list && n_list > 0) {
     const int n_items = 3 * qw;
-#ifndef DCTAE_C7_IPB
-#define DCTAE_C7_IPB 2
-#endif
-    const int grid = cols7_grid(n_list, qw, thr ? DCTAE_C7_IPB : 2);
+    constexpr int kC7Ipb = 2;
+    const int grid = cols7_grid(n_list, qw, thr ? kC7Ipb : 2);
     if (thr)
-      hipLaunchKernelGGL((k_fft_cols7<true, DCTAE_C7_IPB, true>), dim3(grid), dim3(256), 0, s, imgs, list, n_list,
+      hipLaunchKernelGGL((k_fft_cols7<true, kC7Ipb, true>), dim3(grid), dim3(256), 0, s, imgs, list, n_list,
                          n_items, qw, ws, tw, post, ep, sk);
     else
       hipLaunchKernelGGL((k_fft_cols7<false, 2, true>), dim3(grid), dim3(256), 0, s, imgs, list, n_list, n_items, qw,
                          ws, tw, post, ep, sk);
     return;
   }
-#define DCTAE_COLS4(NN, RR, T)                                                                                  \
-  hipLaunchKernelGGL((k_fft_cols4<NN, RR, 14, T>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, tw, post, ep, sk)
-  if (spec == 1 && thr) DCTAE_COLS4(512, 16, true);
-  else if (spec == 1) DCTAE_COLS4(512, 16, false);
-#ifndef DCTAE_COLS224
-#define DCTAE_COLS224 1
-#endif
-  else if (spec == 2 && DCTAE_COLS224 && thr)
+  if (spec == 1 && thr)
+    hipLaunchKernelGGL((k_fft_cols4<512, 16, 14, true>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, tw, post, ep,
+                       sk);
+  else if (spec == 1)
+    hipLaunchKernelGGL((k_fft_cols4<512, 16, 14, false>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, tw, post,
+                       ep, sk);
+  else if (spec == 2 && thr)
     hipLaunchKernelGGL((k_cols224<true>), dim3(8 * (((n_blocks + 1) / 2 + 7) / 8)), dim3(256), 0, s, imgs, blocks,
                        n_blocks, ws, tw, post, ep, sk);
-  else if (spec == 2 && DCTAE_COLS224)
+  else if (spec == 2)
     hipLaunchKernelGGL((k_cols224<false>), dim3(8 * (((n_blocks + 1) / 2 + 7) / 8)), dim3(256), 0, s, imgs, blocks,
                        n_blocks, ws, tw, post, ep, sk);
-  else if (spec == 2 && thr) DCTAE_COLS4(224, 7, true);
-  else if (spec == 2) DCTAE_COLS4(224, 7, false);
-#undef DCTAE_COLS4
 }
 
 }  // namespace dctae

@@ -461,12 +461,9 @@ __global__ __launch_bounds__(256, (SH == 0 && NC == 3) ? 1 : 2) void k_gemm_x3(c
 // two into the fp16 range, so a piece pair carries 22 significant bits and
 // the dropped terms (a1 b1, the pieces' residuals) are <= 3 x 2^-22 |a b|
 // (~0.1 of the fp32 rounding of k_gemm_f32's sums; half the MFMAs of k_gemm_x3)
-#ifndef DCTAE_H2_WPE
-#define DCTAE_H2_WPE 2
-#endif
 template <int NC, int SH>
-__global__ __launch_bounds__(256, DCTAE_H2_WPE) void k_gemm_h2(const GemmProblem* __restrict__ probs,
-                                                  const TileRef* __restrict__ tiles) {
+__global__ __launch_bounds__(256, 2) void k_gemm_h2(const GemmProblem* __restrict__ probs,
+                                      const TileRef* __restrict__ tiles) {
   using S = X3Shape<NC, SH>;
   __shared__ Pieces<S::TM, 2> As[S::NA];
   __shared__ Pieces<S::TN, 2> Bs[S::NB];
@@ -491,29 +488,17 @@ __global__ __launch_bounds__(256, DCTAE_H2_WPE) void k_gemm_h2(const GemmProblem
 // positions of the 256-byte bank window: with s ^ (r & 7) rows r and r + 8
 // collided, PMC 37 % of the kernel's LDS cycles in bank conflicts);
 // a B row 4 slots of 8 halves at kq ^ swz(r), as Pieces.
-#ifndef DCTAE_GEMM_DMA
-#define DCTAE_GEMM_DMA 1
-#endif
-#ifndef DCTAE_GEMM_DMA_BR   // the matrix fragments in registers (needs NS >= 3)
-#define DCTAE_GEMM_DMA_BR 0
-#endif
-#ifndef DCTAE_GEMM_DMA_NS   // ring stages
-#define DCTAE_GEMM_DMA_NS 2
-#endif
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-// NS ring stages; BR: the pre-split matrix's fragments loaded straight into
-// registers one chunk ahead (the ring then holds the image operand only)
-template <int NS, bool BR>
 struct H2rShape {
   static constexpr int NC = 3, TM = 64, TN = 128;
+  static constexpr int NS = 2;                              // ring stages
   static constexpr int A_CH = TM * XK * 4;                  // 8 KB per channel
   static constexpr int A_BYTES = NC * A_CH;                 // 24 KB
   static constexpr int B_PL = TN * XK * 2;                  // 8 KB per plane
-  static constexpr int STAGE = A_BYTES + (BR ? 0 : 2 * B_PL);
+  static constexpr int STAGE = A_BYTES + 2 * B_PL;
   static constexpr int BPC = (160 * 1024) / (NS * STAGE) < 4 ? (160 * 1024) / (NS * STAGE) : 4;   // blocks per CU
-  static constexpr int NDMA_A = 2 * NC;                     // buffer_load ... lds per wave per chunk: image
-  static constexpr int NDMA = NDMA_A + (BR ? 0 : 4);        //   ... and matrix
+  static constexpr int NDMA = 2 * NC + 4;                   // buffer_load ... lds per wave per chunk: image and matrix
 };
 
 // Workgroup barrier for LDS hand-offs only: this wave's LDS writes done, then
@@ -557,14 +542,12 @@ __device__ __forceinline__ void wait_vm() {
   __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
 }
 
-template <int NS, bool BR>
-__global__ __launch_bounds__(256, (H2rShape<NS, BR>::BPC)) void k_gemm_h2r(const GemmProblem* __restrict__ probs,
-                                                                        const TileRef* __restrict__ tiles) {
-  using S = H2rShape<NS, BR>;
-  constexpr int NC = S::NC, TM = S::TM, TN = S::TN, A_CH = S::A_CH, A_BYTES = S::A_BYTES, B_PL = S::B_PL;
+__global__ __launch_bounds__(256, H2rShape::BPC) void k_gemm_h2r(const GemmProblem* __restrict__ probs,
+                                                               const TileRef* __restrict__ tiles) {
+  using S = H2rShape;
+  constexpr int NS = S::NS, NC = S::NC, TM = S::TM, TN = S::TN, A_CH = S::A_CH, A_BYTES = S::A_BYTES, B_PL = S::B_PL;
   constexpr int STAGE = S::STAGE;
   static_assert(S::BPC >= 1 && NS >= 2, "k_gemm_h2r: ring");
-  static_assert(!BR || NS >= 3, "k_gemm_h2r: BR waits assume a chunk in flight behind the matrix loads");
   __shared__ __attribute__((aligned(16))) uint8_t ring[NS * STAGE];
   const TileRef tr = tiles[blockIdx.x];
   if (tr.problem < 0) return;   // padding of an XCD-dealt list
@@ -616,8 +599,6 @@ __global__ __launch_bounds__(256, (H2rShape<NS, BR>::BPC)) void k_gemm_h2r(const
     const int row = 16 * (4 * h + wave) + (lane >> 2), kq = (lane & 3) ^ swz(row);
     boff[h] = ((n0 + row) * p.xs_ld + 8 * kq) * 2;
   }
-  // in registers (BR): this lane's fragments, rows wn 64 + 32 x + l32, k quad 2 ks + half
-  const int bro = ((n0 + wn * 64 + l32) * p.xs_ld + 8 * half) * 2;
   auto dma = [&](int st, int k0) {
     uint8_t* base = ring + st * STAGE;
 #pragma unroll
@@ -626,26 +607,12 @@ __global__ __launch_bounds__(256, (H2rShape<NS, BR>::BPC)) void k_gemm_h2r(const
       __builtin_amdgcn_raw_ptr_buffer_load_lds(arsrc[c], (lds_void_t*)(base + c * A_CH + (4 * h + wave) * 1024), 16,
                                                (int)((uint32_t)aoff[h] + (uint32_t)k0 * 4u), 0, 0, 0);
     }
-    if constexpr (!BR) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int pl = j >> 1, h = j & 1;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(brsrc, (lds_void_t*)(base + A_BYTES + pl * B_PL + (4 * h + wave) * 1024),
-                                                 16, boff[h] + k0 * 2 + pl * xsp2, 0, 0, 0);
-      }
+    for (int j = 0; j < 4; ++j) {
+      const int pl = j >> 1, h = j & 1;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(brsrc, (lds_void_t*)(base + A_BYTES + pl * B_PL + (4 * h + wave) * 1024), 16,
+                                               boff[h] + k0 * 2 + pl * xsp2, 0, 0, 0);
     }
-  };
-  typedef bf16x8 BFrag[XK / 16][2][2];   // [ks][x][plane]
-  auto load_b = [&](BFrag& f, int k0) {
-#pragma unroll
-    for (int ks = 0; ks < XK / 16; ++ks)
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-          f[ks][x][pl] = __builtin_bit_cast(
-              bf16x8, __builtin_amdgcn_raw_buffer_load_b128(brsrc, bro + (32 * x * p.xs_ld + k0 + 16 * ks) * 2 + pl * xsp2,
-                                                            0, 0));
   };
   floatx16 acc[NC][2];
 #pragma unroll
@@ -655,7 +622,7 @@ __global__ __launch_bounds__(256, (H2rShape<NS, BR>::BPC)) void k_gemm_h2r(const
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[c][x][r] = 0.0f;
   const int ra = wm * 32 + l32;   // this lane's A row in the tile
-  auto compute = [&](int st, int k0, const BFrag& bf) {
+  auto compute = [&](int st, int k0) {
     const uint8_t* base = ring + st * STAGE;
     const float* Af = reinterpret_cast<const float*>(base);
     const uint16_t* Bp = reinterpret_cast<const uint16_t*>(base + A_BYTES);
@@ -668,7 +635,7 @@ __global__ __launch_bounds__(256, (H2rShape<NS, BR>::BPC)) void k_gemm_h2r(const
         const int rb = wn * 64 + 32 * x + l32;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
-          b[x][pl] = BR ? bf[ks][x][pl] : *reinterpret_cast<const bf16x8*>(Bp + pl * (B_PL / 2) + rb * XK + 8 * (kq ^ swz(rb)));
+          b[x][pl] = *reinterpret_cast<const bf16x8*>(Bp + pl * (B_PL / 2) + rb * XK + 8 * (kq ^ swz(rb)));
       }
       const int kb = k0 + 8 * kq;   // this lane's first k
 #pragma unroll
@@ -701,34 +668,26 @@ __global__ __launch_bounds__(256, (H2rShape<NS, BR>::BPC)) void k_gemm_h2r(const
       }
     }
   };
-  // NS - 1 image chunks in flight: chunk i lands in stage i % NS.  Issue
-  // order per iteration i: [matrix chunk i + 1 (BR)] [image chunk i + NS - 1];
-  // at the top of iteration i this wave's chunk-i loads (and the matrix's) are
-  // done once at most the younger image chunks' loads are outstanding (all,
-  // near the end); the barrier makes that every wave's and frees stage
-  // (i - 1) % NS for chunk i + NS - 1
+  // NS - 1 chunks in flight: chunk i lands in stage i % NS.  At the top of
+  // iteration i this wave's chunk-i loads are done once at most the younger
+  // chunks' loads are outstanding (all, near the end); the barrier makes that
+  // every wave's and frees stage (i - 1) % NS for chunk i + NS - 1
   const int nk = (p.K + XK - 1) / XK;
-  BFrag bf0, bf1;
-  if constexpr (BR) load_b(bf0, 0);
 #pragma unroll
   for (int i = 0; i < NS - 1; ++i)
     if (i < nk) dma(i, i * XK);
-  auto step = [&](int i, const BFrag& cur, BFrag& nxt) {
+  auto step = [&](int i) {
     if (NS == 2 || i + NS - 2 >= nk)
       wait_vm<0>();
-    else if (BR)
-      wait_vm<S::NDMA_A>();   // image chunk i + 1 (NS = 3) may be outstanding
     else
       wait_vm<S::NDMA * (NS - 2)>();
     __syncthreads();
-    if constexpr (BR)
-      if (i + 1 < nk) load_b(nxt, (i + 1) * XK);
     if (i + NS - 1 < nk) dma((i + NS - 1) % NS, (i + NS - 1) * XK);
-    compute(i % NS, i * XK, cur);
+    compute(i % NS, i * XK);
   };
   for (int i = 0; i < nk; i += 2) {
-    step(i, bf0, bf1);
-    if (i + 1 < nk) step(i + 1, bf1, bf0);
+    step(i);
+    if (i + 1 < nk) step(i + 1);
   }
   __syncthreads();   // the ring is reused below
   uint32_t mx = 0;
@@ -959,9 +918,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_h2c(const GemmProblem* __restri
 void launch_gemm_h2(const GemmProblem* probs, const TileRef* tiles, int n_tiles, hipStream_t s, int share, bool dma,
                     bool dma_cols) {
   if (n_tiles <= 0) return;
-  if (share == 1 && dma && DCTAE_GEMM_DMA)
-    hipLaunchKernelGGL((k_gemm_h2r<DCTAE_GEMM_DMA_NS, DCTAE_GEMM_DMA_BR != 0>), dim3(n_tiles), dim3(256), 0, s, probs,
-                       tiles);
+  if (share == 1 && dma)
+    hipLaunchKernelGGL(k_gemm_h2r, dim3(n_tiles), dim3(256), 0, s, probs, tiles);
   else if (share == 1)
     hipLaunchKernelGGL((k_gemm_h2<3, 1>), dim3(n_tiles), dim3(256), 0, s, probs, tiles);
   else if (dma_cols)
@@ -987,29 +945,15 @@ void launch_gemm_h2(const GemmProblem* probs, const TileRef* tiles, int n_tiles,
 // matrices stream through a two-stage LDS ring (LDS DMA), the pixels two
 // chunks ahead in registers.
 // Scale: the image's |max| (k_gemm_h2's operand scale) is unknown before the
-// transform, so the first pass splits at a fixed 2^DCTAE_FUSED_SE and records
+// transform, so the first pass splits at a fixed 2^kFusedSE and records
 // the |max| of the folded values; an image with a value outside the safe fp16
 // range (|v| 2^SE >= 2^15, or not finite) is flagged, and the fix-up launch
 // (fix = 1, flagged images only, grid-stride) redoes it at the scale k_gemm_h2
 // derives from that |max| -- the old path's arithmetic for those images.
 // ---------------------------------------------------------------------------
-#ifndef DCTAE_FUSED_SE
-#define DCTAE_FUSED_SE 11
-#endif
-// 1: the colour transform of chunk i + 1 interleaved with chunk i's MFMAs
-// (double-buffered pieces; TN = 224 so that the ring and both piece buffers
-// fit 160 KB of LDS), 0: transform and MFMA phases between two barriers.
-// Off: on the config-4 batch the interleaved form encoded 3-6 % of calls
-// differently from the first call (whole coefficient columns of the first
-// images' low kx -- stale or unwritten matrix rows read by the MFMAs; NaN on
-// a fresh GPU without the persistent loop), the two-barrier form 0 of 690
-// (tools/c4_stress.py); with vmcnt(0) at each step top 0 of 100, but slower
-#ifndef DCTAE_FUSED_PIPE
-#define DCTAE_FUSED_PIPE 0
-#endif
-#ifndef DCTAE_FUSED_DYN
-#define DCTAE_FUSED_DYN 1   // persistent first pass with per-XCD tile counters (below)
-#endif
+// The form that interleaved chunk i + 1's colour transform with chunk i's
+// MFMAs encoded the config-4 batch non-deterministically and was removed.
+constexpr int kFusedSE = 11;       // the first pass's operand scale 2^kFusedSE
 constexpr int kFusedPairs = 16;    // row pairs per block
 constexpr int kFusedTN = 256;      // output columns per parity
 
@@ -1018,12 +962,11 @@ __global__ __launch_bounds__(512, 1) void k_rows_fused(const GemmProblem* __rest
                                                       const ImgDesc* __restrict__ imgs, const float* __restrict__ rgb,
                                                       ColorMats cm, uint32_t* __restrict__ amax, int* __restrict__ flags,
                                                       int n_img, int fix) {
-  constexpr bool PIPE = DCTAE_FUSED_PIPE != 0;
-  constexpr int TN = PIPE ? 224 : kFusedTN, NPR = kFusedPairs;
+  constexpr int TN = kFusedTN, NPR = kFusedPairs;
   constexpr int B_PL = TN * XK * 2;          // 16 KB: one plane of one parity's matrix chunk
-  constexpr int B_ST = 4 * B_PL;             // 64 KB (56 KB, PIPE): 2 parities x 2 planes
+  constexpr int B_ST = 4 * B_PL;             // 64 KB: 2 parities x 2 planes
   constexpr int A_CQ = 2 * NPR * XK;         // halves per (parity, channel, piece): 32 rows x 32 k
-  __shared__ __attribute__((aligned(16))) uint8_t lds[2 * B_ST + (PIPE ? 2 : 1) * 12 * A_CQ * 2];   // 152 / 160 KB
+  __shared__ __attribute__((aligned(16))) uint8_t lds[2 * B_ST + 12 * A_CQ * 2];   // 152 KB
   uint16_t* As = reinterpret_cast<uint16_t*>(lds + 2 * B_ST);
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l32 = lane & 31;
   // the wave index as a uniform value: the parity's matrix descriptor and the
@@ -1033,12 +976,12 @@ __global__ __launch_bounds__(512, 1) void k_rows_fused(const GemmProblem* __rest
   const int pw = wave >> 2, wc = wave & 3;   // this wave's parity and 64-column slice
   const float gam = 0.430000007152557373046875f;
   if (fix && flags[n_img] == 0) return;      // fix-up: no image of the job flagged
-  // DCTAE_FUSED_DYN (first pass): a persistent grid taking tiles from
+  // The first pass: a persistent grid taking tiles from
   // per-XCD counters (flags[n_img + 1 + x]): block b runs on XCD b % 8 and
   // takes the dealt list's positions x + 8 k of its XCD lane in counter order,
   // so the image-per-XCD dealing holds without a static split's imbalance, and
   // the next tile's counter value is fetched while this tile runs
-  const bool dyn = DCTAE_FUSED_DYN && !fix;
+  const bool dyn = !fix;
   const int xl = (int)(blockIdx.x & 7);
   int* ctr = flags + n_img + 1 + xl;
   for (int t = blockIdx.x; t < n_tiles;) {
@@ -1065,7 +1008,7 @@ __global__ __launch_bounds__(512, 1) void k_rows_fused(const GemmProblem* __rest
     const int H = d.H, W = d.W, Hh = (H + 1) >> 1, Ku = pu.K, Kv = pv.K;
     const int j0 = tr.tile * NPR;
     // operand scale 2^se: fixed in the first pass, k_gemm_h2's rule on the recorded |max| in the fix-up
-    int se = DCTAE_FUSED_SE;
+    int se = kFusedSE;
     if (fix) {
       const uint32_t mb = amax[2 * li];
       se = 0;
@@ -1220,99 +1163,33 @@ __global__ __launch_bounds__(512, 1) void k_rows_fused(const GemmProblem* __rest
         }
     };
     const int nk = (Ku + XK - 1) / XK;
-    if constexpr (!PIPE) {
-      // Pixels two chunks ahead (pxa: even chunks, pxb: odd), the matrices one;
-      // issue order per step i: [matrices i + 1] [pixels i + 2], so at its top at
-      // most pixels i + 1's 12 loads may be outstanding.  Every step issues the
-      // same loads (past the last chunk: clamped pixels, matrix offsets reading
-      // zeros), and the loop body is unconditional, so the compiler's own waits
-      // on the pixel registers count exactly.
-      auto step = [&](int i, Px& cur) {
-        wait_vm<12>();      // this wave's pixels and matrix chunk i
-        lds_barrier();      // every wave's; chunk i - 1's MFMAs done (the pieces and stage (i + 1) % 2 free)
-        dma_b((i + 1) & 1, (i + 1) * XK);
-        transform(cur, i * XK, As);
-        load_rgb(cur, (i + 2) * XK);
-        lds_barrier();      // the pieces of chunk i
+    // Pixels two chunks ahead (pxa: even chunks, pxb: odd), the matrices one;
+    // issue order per step i: [matrices i + 1] [pixels i + 2], so at its top at
+    // most pixels i + 1's 12 loads may be outstanding.  Every step issues the
+    // same loads (past the last chunk: clamped pixels, matrix offsets reading
+    // zeros), and the loop body is unconditional, so the compiler's own waits
+    // on the pixel registers count exactly.
+    auto step = [&](int i, Px& cur) {
+      wait_vm<12>();      // this wave's pixels and matrix chunk i
+      lds_barrier();      // every wave's; chunk i - 1's MFMAs done (the pieces and stage (i + 1) % 2 free)
+      dma_b((i + 1) & 1, (i + 1) * XK);
+      transform(cur, i * XK, As);
+      load_rgb(cur, (i + 2) * XK);
+      lds_barrier();      // the pieces of chunk i
 #pragma unroll
-        for (int ks = 0; ks < XK / 16; ++ks)
+      for (int ks = 0; ks < XK / 16; ++ks)
 #pragma unroll
-          for (int c = 0; c < 3; ++c) mfma_unit(i & 1, As, ks, c);
-      };
-      load_rgb(pxa, 0);
-      dma_b(0, 0);
-      load_rgb(pxb, XK);
-      int i = 0;
-      for (; i + 1 < nk; i += 2) {
-        step(i, pxa);
-        step(i + 1, pxb);
-      }
-      if (i < nk) step(i, pxa);
-    } else {
-      // DCTAE_FUSED_PIPE: the transform of chunk i + 1 interleaved with chunk i's
-      // MFMAs (double-buffered pieces As / As + 12 A_CQ), one barrier per chunk.
-      // Issue order per step i: [matrices i + 1] [pixels i + 3]; at its top the
-      // wave needs matrices i and pixels i + 1, pixels i + 2 may be in flight.
-      uint16_t* A0 = As;
-      uint16_t* A1 = As + 12 * A_CQ;
-      auto step = [&](int i, Px& cur, const uint16_t* Ac, uint16_t* An) {
-#ifdef DCTAE_FUSED_SB   // pin the issue order the counted wait assumes (no load moved across it)
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-#if defined(DCTAE_FUSED_WAIT0)
-        wait_vm<0>();
-#elif !defined(DCTAE_FUSED_EARLYWAIT)
-        wait_vm<12>();
-#endif
-        lds_barrier();      // pieces of chunk i from every wave; chunk i - 1's MFMAs done (An, stage (i + 1) % 2 free)
-        dma_b((i + 1) & 1, (i + 1) * XK);
-        const int kn = (i + 1) * XK;
-        mfma_unit(i & 1, Ac, 0, 0);
-        pix(cur, 0);
-        mfma_unit(i & 1, Ac, 0, 1);
-        pix(cur, 1);
-        mfma_unit(i & 1, Ac, 0, 2);
-        pix(cur, 2);
-        mfma_unit(i & 1, Ac, 1, 0);
-        pix(cur, 3);
-#ifdef DCTAE_FUSED_EARLYWAIT
-        // (experiment) the pixels of chunk i + 3 issued as soon as cur is
-        // consumed, and the wait for matrices i + 1 two MFMA units before the
-        // next barrier instead of right before it
-        load_rgb(cur, (i + 3) * XK);
-        mfma_unit(i & 1, Ac, 1, 1);
-        fold(kn, 0, An);
-        fold(kn, 1, An);
-#ifdef DCTAE_FUSED_SB
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-        wait_vm<12>();
-        mfma_unit(i & 1, Ac, 1, 2);
-        fold(kn, 2, An);
-#else
-        mfma_unit(i & 1, Ac, 1, 1);
-        fold(kn, 0, An);
-        fold(kn, 1, An);
-        mfma_unit(i & 1, Ac, 1, 2);
-        fold(kn, 2, An);
-        load_rgb(cur, (i + 3) * XK);
-#endif
-      };
-      load_rgb(pxa, 0);
-      load_rgb(pxb, XK);
-      dma_b(0, 0);
-      transform(pxa, 0, A0);
-      load_rgb(pxa, 2 * XK);
-#ifdef DCTAE_FUSED_EARLYWAIT
-      wait_vm<12>();   // matrices 0
-#endif
-      int i = 0;
-      for (; i + 1 < nk; i += 2) {
-        step(i, pxb, A0, A1);
-        step(i + 1, pxa, A1, A0);
-      }
-      if (i < nk) step(i, pxb, A0, A1);
+        for (int c = 0; c < 3; ++c) mfma_unit(i & 1, As, ks, c);
+    };
+    load_rgb(pxa, 0);
+    dma_b(0, 0);
+    load_rgb(pxb, XK);
+    int i = 0;
+    for (; i + 1 < nk; i += 2) {
+      step(i, pxa);
+      step(i + 1, pxb);
     }
+    if (i < nk) step(i, pxa);
     wait_vm<0>();   // no LDS DMA may outlive the loop (the LDS is reused, and released at exit)
     const GemmProblem& p = pw ? pv : pu;
     const int N = p.N;
@@ -1403,14 +1280,15 @@ __global__ __launch_bounds__(512, 1) void k_rows_fused(const GemmProblem* __rest
 }
 
 int fused_pairs_per_block() { return kFusedPairs; }
-int fused_max_n() { return DCTAE_FUSED_PIPE ? 224 : kFusedTN; }
+int fused_max_n() { return kFusedTN; }
 
 void launch_rows_fused(const GemmProblem* probs, const TileRef* tiles, int n_tiles, const ImgDesc* imgs,
                        const float* rgb, const ColorMats& cm, uint32_t* amax, int* flags, int n_img, hipStream_t s,
                        bool fixup) {
   if (n_tiles <= 0) return;
-  // the fix-up: a short grid-stride launch (every block exits at once when no image is flagged)
-  const int g = fixup || DCTAE_FUSED_DYN ? std::min((n_tiles + 7) & ~7, 256) : n_tiles;
+  // the persistent first pass, or the fix-up's short grid-stride launch (every
+  // block exits at once when no image is flagged)
+  const int g = std::min((n_tiles + 7) & ~7, 256);
   hipLaunchKernelGGL(k_rows_fused, dim3(g), dim3(512), 0, s, probs, tiles, n_tiles, imgs, rgb, cm, amax, flags, n_img,
                      fixup ? 1 : 0);
 }

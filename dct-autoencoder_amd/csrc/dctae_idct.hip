@@ -120,11 +120,7 @@ void launch_dec_map(int64_t n_tok, const ImgDesc* imgs, const DecodeArgs& a, int
 // the bank rule of MI355X_MICROARCH.md, SQ_LDS_BANK_CONFLICT 91.5 M per launch
 // before; the kernel time did not move: it is latency-bound).  Rows
 // 448 .. 511 map onto themselves (the zero fill is unchanged).
-#ifdef DCTAE_NO_XROW
-__device__ __forceinline__ int xrow(int y) { return y; }
-#else
 __device__ __forceinline__ int xrow(int y) { return y ^ ((y >> 4) & 3); }
-#endif
 
 struct IColsLds {
   union {
@@ -525,9 +521,9 @@ __global__ __launch_bounds__(256) void k_idct_rows2(const ImgDesc* __restrict__ 
 // ---------------------------------------------------------------------------
 // k_idct_cols512b: the column DCT-III of 512 x 512 images at 32 x 32 kept
 // tiles with the encode's register-resident FFT (fft256_group, dctae_rows512.h)
-// and U written straight from registers in the band layout U'[c][y / 4][kx][4]
-// (u4_index: band16 by default, rows 4 m .. 4 m + 3 of one column = one
-// float4, natural order), read by k_idct_rows512<448, true>.  Block = (channel,
+// and U written straight from registers in the band layout U' (u4_index:
+// band16, rows 4 m .. 4 m + 3 of one column = one float4, natural order),
+// read by k_idct_rows512<448, true>.  Block = (channel,
 // tile strip) x IPB images, one 16-lane group per column (groups 14 / 15
 // repeat column 13 and store the same values), XCD-dealt like k_cols512b.
 // Per image: tokens -> X (LDS, icols_fill_x) | barrier | lane j of column col
@@ -547,26 +543,14 @@ struct ICols512bLds {
   float4 pre[256];                // (conj a_k, conj b_k)
 };                                // 40,960 B: 4 blocks per CU
 
-#ifndef DCTAE_IC5B_WPE
-#define DCTAE_IC5B_WPE 0
-#endif
-// 1: the token map entries two images ahead, the codes one image ahead (issued
-// right after the expansion); 0: map one ahead, codes after the FFT
-#ifndef DCTAE_IC5B_AHEAD2
-#define DCTAE_IC5B_AHEAD2 1
-#endif
 template <int IPB>
-__global__ __launch_bounds__(256)
-#if DCTAE_IC5B_WPE
-__attribute__((amdgpu_waves_per_eu(DCTAE_IC5B_WPE)))
-#endif
-void k_idct_cols512b(const ImgDesc* __restrict__ imgs, int n_img,
+__global__ __launch_bounds__(256) void k_idct_cols512b(const ImgDesc* __restrict__ imgs, int n_img,
                                                        float* __restrict__ ws, const int32_t* __restrict__ map,
                                                        const float2* __restrict__ tw, const float4* __restrict__ pre,
                                                        DecodeArgs a) {
 #pragma clang fp contract(fast)
   constexpr int M = 256, KS = 14, KW = 448, per_x = 12;   // 96 items = 3 channels x 32 strips, 12 per XCD lane
-  constexpr int ustep = 16 * KW * 16;   // bytes between band4 = m and m + 16 (both layouts)
+  constexpr int ustep = 16 * KW * 16;   // bytes between band4 = m and m + 16
   __shared__ ICols512bLds L;
   const int b = blockIdx.x, slot = b >> 3;
   const int t = (b & 7) * per_x + slot % per_x, i0 = (slot / per_x) * IPB;
@@ -580,18 +564,15 @@ void k_idct_cols512b(const ImgDesc* __restrict__ imgs, int n_img,
   const int G = tid >> 4, j = tid & 15;
   const int col = min(G, KS - 1);
   const int uo = u4_index(j, KS * strip + col) * 16;   // band4 = j + 16 i at + i * ustep
-  // the tokens of image u + 1 in flight during image u: its map entries are
-  // loaded right after image u's expansion, its codes (dependent on them)
-  // after image u's FFT, before image u's U stores
+  // the token map entries two images ahead, the codes (dependent on them) one
+  // image ahead, issued right after the expansion
   IcTok tk, tm;   // this image's map entries + codes; the next image's map entries
   icols_map(i0, imgs[i0], c, strip, map, a, tk);
   icols_codes(a, tk);
-#if DCTAE_IC5B_AHEAD2
   if (IPB > 1) {
     const int i1 = min(i0 + 1, n_img - 1);
     icols_map(i1, imgs[i1], c, strip, map, a, tm);
   }
-#endif
 #pragma unroll
   for (int u = 0; u < IPB; ++u) {
     const int img = i0 + u;
@@ -599,20 +580,14 @@ void k_idct_cols512b(const ImgDesc* __restrict__ imgs, int n_img,
     const ImgDesc d = imgs[img];
     __syncthreads();   // tables (u = 0) / the previous image's transposes (x aliases xch)
     icols_expand(tk, a, vt, L.u.x, false);
-    IcTok tn;
-#if DCTAE_IC5B_AHEAD2
     // the next image's codes (its map entries arrived during this image's
     // predecessor) and the map entries of the one after, all in flight
     // through this image's transform and stores (unconditional: past the end
     // of the list the last image reloads itself)
-    tn = tm;
+    IcTok tn = tm;
     if (u + 1 < IPB) icols_codes(a, tn);
     const int img_n2 = min(img + 2, n_img - 1);
     if (u + 2 < IPB) icols_map(img_n2, imgs[img_n2], c, strip, map, a, tm);
-#else
-    const int img_n = min(img + 1, n_img - 1);   // unconditional (the last image reloads itself)
-    if (u + 1 < IPB) icols_map(img_n, imgs[img_n], c, strip, map, a, tn);
-#endif
     __syncthreads();
     // conj Z_k, k = j + 16 i (Ys[M + k] = 0 for i >= 12, Ys[N - k] = 0 for k <= 64)
     cf v[16];
@@ -637,9 +612,6 @@ void k_idct_cols512b(const ImgDesc* __restrict__ imgs, int n_img,
     }
     __syncthreads();   // every group's X reads before the transposes
     fft256_group(v, L.u.xch[G], j, j, L.tw2);
-#if !DCTAE_IC5B_AHEAD2
-    if (u + 1 < IPB) icols_codes(a, tn);
-#endif
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(ws + d.ws_t + (int64_t)c * 512 * KW, 0, 512 * KW * 4,
                                                         0x00020000);
 #if defined(DCTAE_PROFILING) && defined(DCTAE_IC_ABL)
@@ -654,18 +626,16 @@ void k_idct_cols512b(const ImgDesc* __restrict__ imgs, int n_img,
       const float px = mirror16(v[15 - i].x), py = mirror16(v[15 - i].y);
       __builtin_amdgcn_raw_buffer_store_b128(
           (v4u){__float_as_uint(v[i].x), __float_as_uint(-py), __float_as_uint(-v[i].y), __float_as_uint(px)}, rsrc,
-          uo, i * ustep, DCTAE_U_ST_AUX);
+          uo, i * ustep, kUStAux);
     }
     if (u + 1 < IPB) tk = tn;
   }
 }
 
-#ifndef DCTAE_IC5B_IPB
-#define DCTAE_IC5B_IPB 12   // images per block (same-box A/Bs, decode 1024 x 512^2: 4 1.98, 6 1.93, 8 1.925 / 1.960, 12 1.910 / 1.945, 16 2.19 ms)
-#endif
 void launch_idct_cols512b(const ImgDesc* imgs, int n_img, float* ws, const int32_t* map, const float2* tw,
                           const float4* pre, const DecodeArgs& a, hipStream_t s) {
-  constexpr int IPB = DCTAE_IC5B_IPB;
+  // images per block (same-box A/Bs, decode 1024 x 512^2: 4 1.98, 6 1.93, 8 1.925 / 1.960, 12 1.910 / 1.945, 16 2.19 ms)
+  constexpr int IPB = 12;
   const int grid = 8 * 12 * ((n_img + IPB - 1) / IPB);
   if (n_img > 0)
     hipLaunchKernelGGL((k_idct_cols512b<IPB>), dim3(grid), dim3(256), 0, s, imgs, n_img, ws, map, tw, pre, a);

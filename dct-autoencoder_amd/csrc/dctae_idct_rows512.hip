@@ -43,8 +43,8 @@ struct IRows512Lds {
 
 }  // namespace
 
-// BAND: U in the band layout U'[c][y / 4][kx][4] of k_idct_cols512b (element
-// (y, kx) at u4_index(y / 4, kx) * 4 + y % 4); otherwise row-major
+// BAND: U in the band layout U' of k_idct_cols512b (element (y, kx) at
+// u4_index(y / 4, kx) * 4 + y % 4); otherwise row-major
 // U[c][y][kx] (k_idct_cols512)
 template <int KW, bool BAND>
 __global__ __launch_bounds__(256) void k_idct_rows512(const ImgDesc* __restrict__ imgs, const int2* __restrict__ blocks,
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void k_idct_rows512(const ImgDesc* __restrict_
     // the wave's four rows are one band4 of U': lane (g, j) loads the float4
     // (rows 4 bnd .. + 3) of column kx = j + 16 (4 q + g); the 4 x 4 cross-row
     // transpose (xpose4_rows) then leaves row g's values of the columns
-    // j + 16 (4 q + k), k = 0..3, in the lane (1 KB per wave load at layout 0)
+    // j + 16 (4 q + k), k = 0..3, in the lane
     static_assert(NB % 4 == 0, "B in whole transposes");
     const int bnd = (jb.y >> 2) + wv;
     const float* ub = ws + d.ws_t;
@@ -84,13 +84,7 @@ __global__ __launch_bounds__(256) void k_idct_rows512(const ImgDesc* __restrict_
 #pragma unroll
       for (int q = 0; q < 4 + NB / 4; ++q) {
         const int kx = j + 16 * (4 * q + g);   // q >= 4: B[4 (q - 4) + k] = Ys[M + j + 16 (4 (q - 4) + k)]
-#if DCTAE_U_LD_NT
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f fv = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(ub + c * cstride + (int64_t)u4_index(bnd, kx) * 4));
-        const float4 f = make_float4(fv.x, fv.y, fv.z, fv.w);
-#else
         const float4 f = *reinterpret_cast<const float4*>(ub + c * cstride + (int64_t)u4_index(bnd, kx) * 4);
-#endif
         float r4[4] = {f.x, f.y, f.z, f.w};
         xpose4_rows(r4);
 #pragma unroll
@@ -204,14 +198,8 @@ __global__ __launch_bounds__(256) void k_idct_rows512(const ImgDesc* __restrict_
       o[2][e] = mat3_row(cm.lms2rgb, 2, l0, l1, l2);
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#ifdef DCTAE_DEC_NT
-      typedef float v4f __attribute__((ext_vector_type(4)));
-      __builtin_nontemporal_store((v4f){o[c][0], o[c][1], o[c][2], o[c][3]}, reinterpret_cast<v4f*>(dst + c * hw + 64 * b));
-#else
+    for (int c = 0; c < 3; ++c)
       *reinterpret_cast<float4*>(dst + c * hw + 64 * b) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
-#endif
-    }
   }
 }
 

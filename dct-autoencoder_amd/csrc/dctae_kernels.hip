@@ -77,24 +77,9 @@ __device__ __forceinline__ void block_amax(uint32_t m, uint32_t* dst) {
   }
 }
 
-// cache policy of k_rgb_to_ipt's RGB loads / folded IPT stores: A/B switches,
-// both off (nontemporal measured slower on config 4, round 5: rgb_to_ipt
-// 1.41 -> 1.63 ms with NT loads, 1.93 ms with NT stores)
-#ifndef DCTAE_IPT_ST_NT
-#define DCTAE_IPT_ST_NT 0
-#endif
-#ifndef DCTAE_RGB_LD_NT
-#define DCTAE_RGB_LD_NT 0
-#endif
-__device__ __forceinline__ void ipt_store(float* p, float v) {
-  if (DCTAE_IPT_ST_NT) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
-__device__ __forceinline__ float rgb_load(const float* p) {
-  if (DCTAE_RGB_LD_NT) return __builtin_nontemporal_load(p);
-  return *p;
-}
-
+// The RGB loads and folded IPT stores at the default cache policy
+// (nontemporal measured slower on config 4, round 5: rgb_to_ipt 1.41 -> 1.63
+// ms with NT loads, 1.93 ms with NT stores)
 __global__ __launch_bounds__(256) void k_rgb_to_ipt(const ImgDesc* __restrict__ imgs, const int2* __restrict__ blocks,
                                                     const float* __restrict__ rgb, float* __restrict__ ws,
                                                     ColorMats cm, uint32_t* __restrict__ amax) {
@@ -124,7 +109,7 @@ __global__ __launch_bounds__(256) void k_rgb_to_ipt(const ImgDesc* __restrict__ 
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) px[k][q][c] = rgb_load(src + c * hw + o[q]);
+      for (int c = 0; c < 3; ++c) px[k][q][c] = *(src + c * hw + o[q]);
   }
   uint32_t mx = 0;   // |max| of the values written (k_gemm_h2's operand scale)
 #pragma unroll
@@ -158,12 +143,12 @@ __global__ __launch_bounds__(256) void k_rgb_to_ipt(const ImgDesc* __restrict__ 
       float* ro = dst + c * hw + (int64_t)y * W;
       const float u0 = xp ? a[c] + b[c] : a[c], v0 = a[c] - b[c];
       const float u1 = xp ? c2[c] + d2[c] : c2[c], v1 = c2[c] - d2[c];
-      ipt_store(ro + x, u0);
-      if (xp) ipt_store(ro + Wh + x, v0);
+      *(ro + x) = u0;
+      if (xp) *(ro + Wh + x) = v0;
       if (yp) {
         float* r2 = dst + c * hw + (int64_t)y2 * W;
-        ipt_store(r2 + x, u1);
-        if (xp) ipt_store(r2 + Wh + x, v1);
+        *(r2 + x) = u1;
+        if (xp) *(r2 + Wh + x) = v1;
       }
       mx = max(mx, __float_as_uint(u0) & 0x7fffffffu);
       if (xp) mx = max(mx, __float_as_uint(v0) & 0x7fffffffu);
@@ -529,12 +514,6 @@ __global__ __launch_bounds__(256) void k_tile_epilogue(const ImgDesc* __restrict
 // an image stages the P spectrum rows it covers (contiguous in Y) through LDS
 // with coalesced loads, then one 16-lane group per tile runs
 // token_epilogue_p on its row held in registers.
-#ifndef DCTAE_TEPI_ROWS
-#define DCTAE_TEPI_ROWS 1
-#endif
-#ifndef DCTAE_TEPI_LIST
-#define DCTAE_TEPI_LIST 1   // 0: the grid over every image x 3 max_patch_h (A/B)
-#endif
 // list (nullable): the (local image, 3 h + c) blocks of the images with Y in the
 // workspace, built on the host (grid = list length): a grid over every image x
 // 3 max_patch_h spent most of its blocks exiting on ragged batches
@@ -550,9 +529,8 @@ __global__ __launch_bounds__(256) void k_tile_epilogue_p(const ImgDesc* __restri
   if (h >= d.qh) return;
   const int Kw = d.Kw, ld = Kw + 1;
   const float* Y = ws + d.ws_y + ((int64_t)c * d.Kh + (int64_t)P * h) * Kw;
-#if DCTAE_TEPI_ROWS
   // the tile row's P rows column chunk by column chunk: P independent loads per
-  // thread in flight, no per-element division (the flat loop's e / Kw cost
+  // thread in flight, no per-element division (a flat loop's e / Kw cost
   // ~20 VALU per element and serialised its loads)
   for (int x0 = 0; x0 < Kw; x0 += 256) {
     const int x = x0 + (int)threadIdx.x;
@@ -566,12 +544,6 @@ __global__ __launch_bounds__(256) void k_tile_epilogue_p(const ImgDesc* __restri
       for (int r = 0; r < P; ++r) ys[r * ld + kx] = a[r];
     }
   }
-#else
-  for (int e = threadIdx.x; e < P * Kw; e += 256) {
-    const int r = e / Kw;
-    ys[r * ld + kx_of_col(d, e - r * Kw)] = Y[e];
-  }
-#endif
   __syncthreads();
   const int g16 = threadIdx.x >> 4, j = threadIdx.x & 15;
   const int jr = j < P ? j : 0;
@@ -587,7 +559,7 @@ void launch_tile_epilogue(const ImgDesc* imgs, int n_img, int max_T, const float
                           const EncParams& ep, const TokenSinks& sk, hipStream_t s, const int2* list, int n_list) {
   if (ep.P == 14 && ep.C == 3 && 14 * (14 * ep.maxpw + 1) * sizeof(float) <= 64 * 1024) {
     const size_t lds = (size_t)14 * (14 * ep.maxpw + 1) * sizeof(float);
-    if (list && DCTAE_TEPI_LIST) {
+    if (list) {
       if (n_list > 0)
         hipLaunchKernelGGL(k_tile_epilogue_p<14>, dim3(n_list), dim3(256), lds, s, imgs, ws, ep, sk, list);
     } else {
@@ -695,7 +667,6 @@ __device__ __forceinline__ void gather_tokens(const ImgDesc& d, const uint16_t* 
 // scores in ascending index order = the (score desc, index asc) order above.
 // Tokens per image <= 512 x 6 = 3072 (max_patch 32 x 32, 3 channels); the
 // 256 x 3 instance covers 224^2 images (768 tokens).
-typedef long long v2i64 __attribute__((ext_vector_type(2)));
 typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
 typedef unsigned v2u32s __attribute__((ext_vector_type(2)));
 
@@ -738,15 +709,9 @@ __global__ __launch_bounds__(kSortBS) void k_sort_pack2(const ImgDesc* __restric
     const uint32_t f = order[t];
     const int c = f % C, s = f / C, h = s / d.qw, w = s % d.qw;
     const int64_t o = base + t;
-#ifdef DCTAE_SORT_META_NT
-    __builtin_nontemporal_store((v2i64){(long long)h, (long long)w}, reinterpret_cast<v2i64*>(out.pos + 2 * o));
-    __builtin_nontemporal_store((long long)c, reinterpret_cast<long long*>(out.ch + o));
-    __builtin_nontemporal_store((long long)d.local_id, reinterpret_cast<long long*>(out.ids + o));
-#else
     *reinterpret_cast<longlong2*>(out.pos + 2 * o) = make_longlong2(h, w);
     out.ch[o] = c;
     out.ids[o] = d.local_id;
-#endif
     if (out.key_pad) out.key_pad[o] = 0;
     if (out.scores) out.scores[o] = st.scores[d.tok_off + spos[t]];
   }

@@ -42,12 +42,6 @@ constexpr int kRow = kKp + 8;        // LDS row stride in halves (108 dwords: th
 constexpr int kMw = 8;               // mask words per token (256 features)
 constexpr int kK4 = 49;              // mode 0: float4 per token row (K = 196, conf/patch14-l.json's dim)
 
-// mode 1's inverse-PatchNorm table pieces of a tile: 1 = loaded at the top of
-// the tile's iteration (in flight during its MFMAs), 0 = after its staging
-#ifndef DCTAE_LFQWS_TAB_EARLY
-#define DCTAE_LFQWS_TAB_EARLY 1
-#endif
-
 struct WsInv {
   const int64_t* ch;    // (n) channels of the tokens, or null: no inverse
   const int64_t* pos;   // (n, 2)
@@ -271,7 +265,6 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(2))) v
     const int64_t tok0 = t * TOK;
     load(MODE == 1 ? t + 2 : t + 1);   // past t1: clamped, unused
     f32x4v tm[MODE == 1 ? U1 : 1], tbv[MODE == 1 ? U1 : 1];
-#if DCTAE_LFQWS_TAB_EARLY
     // mode 1: this tile's table pieces (Tb[buf]: staged last iteration), in
     // flight during the MFMAs and the next tile's staging
     if (MODE == 1 && inv.ch) {
@@ -284,7 +277,6 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(2))) v
         tbv[i] = *reinterpret_cast<const f32x4v*>(inv.b + o);
       }
     }
-#endif
     floatx16 acc[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -342,22 +334,7 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(2))) v
       }
     }
     if (t + 1 < t1) store(t + 1, buf ^ 1);
-    if constexpr (MODE == 1) {
-      put_idx(buf);   // Ix[buf] held tile t's indices, read by the staging before the last barrier
-      // this tile's table pieces, in flight during the barrier
-      if (!DCTAE_LFQWS_TAB_EARLY && inv.ch) {
-#pragma unroll
-        for (int i = 0; i < U1; ++i) {
-          const int u = tid + kThr * i, row = u / N4, c4 = u - row * N4;
-          const int64_t tb = u < TOK * N4 ? Tb[buf * TOK + row] : -2;
-          tm[i] = tbv[i] = f32x4v{0.f, 0.f, 0.f, 0.f};
-          if (tb >= 0) {
-            tm[i] = *reinterpret_cast<const f32x4v*>(inv.med + tb + fbase + 4 * c4);
-            tbv[i] = *reinterpret_cast<const f32x4v*>(inv.b + tb + fbase + 4 * c4);
-          }
-        }
-      }
-    }
+    if constexpr (MODE == 1) put_idx(buf);   // Ix[buf] held tile t's indices, read by the staging before the last barrier
     __syncthreads();
     if constexpr (MODE == 0) {
       // (token i, codebook c) pairs of the tile, token-major: contiguous stores
@@ -399,10 +376,6 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(2))) v
   }
 }
 
-#ifndef DCTAE_LFQWS_OUT_NWB
-#define DCTAE_LFQWS_OUT_NWB 4   // project_out: waves per block (4: two blocks per token range; 7: one)
-#endif
-
 int cu_count() {
   static int cached[64] = {0};
   int dev = 0;
@@ -442,9 +415,6 @@ void launch_lfq_ws(int mode, hipStream_t s, const float* x, const int64_t* idx_i
   const WsInv inv{ch, pos, med, nb, eps, maxph, maxpw, err};
   if (mode == 0)
     hipLaunchKernelGGL((k_lfq_ws<0, 2, kNW>), dim3((unsigned)ranges), dim3(64 * kNW), 0, s, x, idx_in, n, K, N, bias,
-                       cd, ncb, scale, idx_out, out, idx16, inv, wsp, NPw, Kp, a_scale, per);
-  else if (DCTAE_LFQWS_OUT_NWB == kNW)
-    hipLaunchKernelGGL((k_lfq_ws<1, 1, kNW>), dim3((unsigned)ranges), dim3(64 * kNW), 0, s, x, idx_in, n, K, N, bias,
                        cd, ncb, scale, idx_out, out, idx16, inv, wsp, NPw, Kp, a_scale, per);
   else
     hipLaunchKernelGGL((k_lfq_ws<1, 1, 4>), dim3((unsigned)(2 * ranges)), dim3(256), 0, s, x, idx_in, n, K, N, bias,

@@ -44,82 +44,18 @@ typedef unsigned v4u __attribute__((ext_vector_type(4)));
 // Measured (1024 x 512^2, same box): layout 0 rows 1.11 / cols 0.735 ms,
 // layout 2 rows 1.08-1.09 / cols 0.607 ms.  Layout 2 at
 // 207 VGPRs (2 waves / SIMD) still beats layout 0 at 156 (3 waves).
+// (This switch outlived the removal of the other settled experiment switches:
+// without layout 0's store offsets in rows512_item_pk -- dead code at layout 2
+// -- hipcc schedules k_rows512pk's instructions in another order.)
 #ifndef DCTAE_TLAYOUT
 #define DCTAE_TLAYOUT 2
 #endif
-// cache-policy bits of the band T' stores (k_rows512pk) and loads (k_cols512b /
-// k_cols512w): 2 = nontemporal (default: T' is written once, read once; its
-// 2.8 GB per 1024 images otherwise churn the L2 / MALL -- same-box A/B, rows
-// 1.089-1.092 -> 1.053-1.054 ms with NT stores, the following sort / pack
-// 0.128 -> 0.108 ms with NT loads), 0 = the default policy
-#ifndef DCTAE_T_ST_AUX
-#define DCTAE_T_ST_AUX 2
-#endif
-#ifndef DCTAE_T_LD_AUX
-#define DCTAE_T_LD_AUX 2
-#endif
-// the decode's band U' (k_idct_cols512b stores, k_idct_rows512 loads): the
-// stores nontemporal (default; same-box A/B r05: decode 2.07-2.12 -> 2.01-2.05
-// ms, cols 0.88-0.90 -> 0.84-0.87, rows 1.10-1.12 -> 1.05-1.08), the loads at
-// the default policy (nontemporal loads: rows 1.10 -> 1.29-1.33 ms)
-#ifndef DCTAE_U_ST_AUX
-#define DCTAE_U_ST_AUX 2
-#endif
-#ifndef DCTAE_U_LD_NT
-#define DCTAE_U_LD_NT 0
-#endif
 static_assert(DCTAE_TLAYOUT == 0 || DCTAE_TLAYOUT == 2, "T' layouts: 0 or 2");
-
-// T' as 12-byte records (DCTAE_T23, band16 layout only): the float4 of a
-// band16 slot (4 rows of one column) is 4 x 23-bit signed mantissas and a
-// nibble of the 8-bit exponent E shared by the record's 16 values (the 4
-// slots of (band16, kx): the same column kx of 16 adjacent rows, so similar
-// magnitudes); x = m 2^(E - 148), |m| < 2^22 against the record's |max| <
-// 2^(E - 126): the largest value keeps 22-23 significant bits (fp32: 24), the
-// others the same absolute step.  E = 255 marks a non-finite value in the
-// record (decoded as NaN).  Slots 0 / 2 carry E's low nibble, 1 / 3 its high
-// one.  T' is written once and read once: 2.06 instead of 2.75 MB per image.
-// Off: measured slower (same box, 1024 x 512^2: rows 1.06 -> 1.10 ms, columns
-// 0.60 -> 0.64 ms, encode 1.83 -> 1.91 ms; codes unchanged vs the oracle) --
-// the pack / unpack VALU and the 12-byte accesses cost more than the 25 %
-// fewer T' bytes save.
-#ifndef DCTAE_T23
-#define DCTAE_T23 0
-#endif
-static_assert(!DCTAE_T23 || DCTAE_TLAYOUT == 2, "12-byte T' records: band16 layout");
-typedef unsigned v3u __attribute__((ext_vector_type(3)));
-
-__device__ __forceinline__ uint32_t quad_max_u32(uint32_t x) {   // max over the 4 lanes of a DPP quad
-  x = max(x, (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xf, 0xf, false));   // quad_perm [1, 0, 3, 2]
-  x = max(x, (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xf, 0xf, false));   // quad_perm [2, 3, 0, 1]
-  return x;
-}
-
-// the record quarter of slot `slot` (the quad's lanes hold slots 0..3 of one record)
-__device__ __forceinline__ v3u t23_pack(float4 f, int slot) {
-  const uint32_t a = max(max(__float_as_uint(f.x) & 0x7fffffffu, __float_as_uint(f.y) & 0x7fffffffu),
-                         max(__float_as_uint(f.z) & 0x7fffffffu, __float_as_uint(f.w) & 0x7fffffffu));
-  const int e = (int)(quad_max_u32(a) >> 23);   // uint order: NaN > Inf > finite, so 255 = non-finite
-  const int E = e < 22 ? 22 : e;
-  const float qm = E == 255 ? 0.0f : __uint_as_float((uint32_t)(275 - E) << 23);   // 2^(148 - E), exact
-  auto q = [&](float x) { return (uint32_t)min(max((int)__builtin_rintf(x * qm), -0x3fffff), 0x3fffff) & 0x7fffffu; };
-  const uint32_t m0 = q(f.x), m1 = q(f.y), m2 = q(f.z), m3 = q(f.w);
-  const uint32_t nib = (slot & 1) ? (uint32_t)E >> 4 : (uint32_t)E & 15u;
-  return (v3u){m0 | (m1 << 23), (m1 >> 9) | (m2 << 14), (m2 >> 18) | (m3 << 5) | (nib << 28)};
-}
-
-// inverse of t23_pack; the 4 lanes of the quad hold the record's 4 slots
-__device__ __forceinline__ float4 t23_unpack(v3u d, int slot) {
-  const uint32_t own = d.z >> 28;
-  const uint32_t oth = (uint32_t)__builtin_amdgcn_mov_dpp((int)own, 0xB1, 0xf, 0xf, false);   // slot ^ 1's nibble
-  const uint32_t E = (slot & 1) ? (oth | (own << 4)) : (own | (oth << 4));
-  const float mul = E == 255u ? __int_as_float(0x7fc00000) : __uint_as_float((E - 21u) << 23);   // 2^(E - 148)
-  const int m0 = (int)(d.x << 9) >> 9;
-  const int m1 = (int)(__builtin_amdgcn_alignbit(d.y, d.x, 23) << 9) >> 9;
-  const int m2 = (int)(__builtin_amdgcn_alignbit(d.z, d.y, 14) << 9) >> 9;
-  const int m3 = (int)(d.z << 4) >> 9;
-  return make_float4((float)m0 * mul, (float)m1 * mul, (float)m2 * mul, (float)m3 * mul);
-}
+// T' as 12-byte records (4 x 23-bit mantissas and a shared exponent per 16
+// values, 2.06 instead of 2.75 MB per image) also measured slower and was
+// removed (same box, 1024 x 512^2: rows 1.06 -> 1.10 ms, columns 0.60 -> 0.64
+// ms, encode 1.83 -> 1.91 ms; codes unchanged vs the oracle): the pack /
+// unpack VALU and the 12-byte accesses cost more than the 25 % fewer T' bytes save.
 __device__ __forceinline__ int t4_index(int band4, int kx) {
 #if DCTAE_TLAYOUT == 0
   return band4 * 448 + kx;
@@ -127,21 +63,20 @@ __device__ __forceinline__ int t4_index(int band4, int kx) {
   return ((band4 >> 2) * 448 + kx) * 4 + (band4 & 3);
 #endif
 }
+// cache-policy bits of the band T' stores (k_rows512pk) and loads (k_cols512b /
+// k_cols512w): 2 = nontemporal (T' is written once, read once; its 2.8 GB per
+// 1024 images otherwise churn the L2 / MALL -- same-box A/B against the
+// default policy, rows 1.089-1.092 -> 1.053-1.054 ms with NT stores, the
+// following sort / pack 0.128 -> 0.108 ms with NT loads)
+constexpr int kTStAux = 2, kTLdAux = 2;
 
-// The decode's band-layout U' (k_idct_cols512b -> k_idct_rows512<448, true>),
-// natural row order in the float4: the same two layouts, chosen apart
-// (DCTAE_ULAYOUT 2 = band16 [y / 16][kx][16], 0 = [y / 4][kx][4]).
-#ifndef DCTAE_ULAYOUT
-#define DCTAE_ULAYOUT 2
-#endif
-static_assert(DCTAE_ULAYOUT == 0 || DCTAE_ULAYOUT == 2, "U' layouts: 0 or 2");
-__device__ __forceinline__ int u4_index(int band4, int kx) {
-#if DCTAE_ULAYOUT == 0
-  return band4 * 448 + kx;
-#else
-  return ((band4 >> 2) * 448 + kx) * 4 + (band4 & 3);
-#endif
-}
+// The decode's band-layout U' (k_idct_cols512b -> k_idct_rows512<448, true>):
+// the same band16 layout, natural row order in the float4.  The stores
+// nontemporal (same-box A/B r05: decode 2.07-2.12 -> 2.01-2.05 ms, cols
+// 0.88-0.90 -> 0.84-0.87, rows 1.10-1.12 -> 1.05-1.08), the loads at the
+// default policy (nontemporal loads: rows 1.10 -> 1.29-1.33 ms)
+__device__ __forceinline__ int u4_index(int band4, int kx) { return ((band4 >> 2) * 448 + kx) * 4 + (band4 & 3); }
+constexpr int kUStAux = 2;
 
 __device__ __forceinline__ float mirror16(float x) {   // lane l <- lane 15 - l of its 16-lane row
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x140, 0xf, 0xf, false));
@@ -184,10 +119,7 @@ __device__ __forceinline__ void rows512_tables(Rows512Tab& L, const float2* __re
 // The IPT keeps the reference's per-pixel op order (util.py:70-82); the FFT
 // is tolerance-tested against the oracle and the generic plan kernels.
 // ---------------------------------------------------------------------------
-#ifndef DCTAE_XCH_PK
-#define DCTAE_XCH_PK 272
-#endif
-constexpr int kXchStridePk = DCTAE_XCH_PK;   // complex slots per row group: 2 KB + 128 B (row groups 0/1 on opposite bank halves)
+constexpr int kXchStridePk = 272;   // complex slots per row group: 2 KB + 128 B (row groups 0/1 on opposite bank halves)
 
 struct Rows512XchPk {
   cf xch[4][4][kXchStridePk];
@@ -323,15 +255,13 @@ __device__ __forceinline__ void xpose4_rows(float (&r)[4]) {
 
 // Row pass output layouts (the channel plane is H x 448 floats either way):
 //  * row-major T[c][y][kx] (band = false): read by the generic column kernels;
-//  * band layout T'[c][y / 4][kx][slot] (band = true, H = 512 with the
-//    columns on k_cols512b), rows 4 b + (0, 2, 3, 1) in slots 0..3 -- the
-//    order of the Makhoul pairs (x0, x2) / (x3, x1) that the column kernel
-//    needs in adjacent registers: the four rows of a wave are one band, so after a
-//    4 x 4 cross-row transpose (xpose4_rows) every lane stores a float4
-//    (rows 4b .. 4b + 3 of one column) and a wave's store covers 64 adjacent
-//    columns = 1 KB contiguous (7 float4 stores + one 4-byte X[M] store per
-//    lane and channel, against 29 scattered 4-byte stores); k_cols512b's
-//    lane j of column kx then loads rows 64 b' + 4 j .. + 3 as one float4.
+//  * band layout T' (band = true, H = 512 with the columns on k_cols512b; t4_index),
+//    rows 4 b + (0, 2, 3, 1) in slots 0..3 of a float4 -- the order of the
+//    Makhoul pairs (x0, x2) / (x3, x1) that the column kernel needs in
+//    adjacent registers: the block's 16 rows of a channel are staged through
+//    LDS and stored as whole 1 KB pieces (7 float4 stores per lane and
+//    channel, against 29 scattered 4-byte stores); k_cols512b's lane j of
+//    column kx then loads rows 64 b' + 4 j .. + 3 as one float4.
 template <bool band>
 __device__ __forceinline__ void rows512_item_pk(Rows512XchPk& X, const Rows512Tab& L, const float* __restrict__ img,
                                                 int H, int y0, float* T, uint32_t plane_bytes, const ColorMats& cm) {
@@ -387,6 +317,7 @@ __device__ __forceinline__ void rows512_item_pk(Rows512XchPk& X, const Rows512Ta
   const int rowo = (y * KW + s) * 4;
   const int rown = (y * KW + (N - 15 * 16) - s) * 4;
   const int rown4 = s >= 1 ? rown : 0x7ffffff0;   // i = 4: k = 64 + s, X[N - k] kept iff s >= 1
+
   // band stores (bytes): after xpose4_rows lane (g, s) of block q holds the
   // wave's four rows of column s + 16 (4 q + g) (X[k]) / N - s - 16 (4 q + g) (X[N - k])
   const int bnd = (y0 >> 2) + wv;
@@ -419,13 +350,7 @@ __device__ __forceinline__ void rows512_item_pk(Rows512XchPk& X, const Rows512Ta
     fft256_group(v, xr, j, s, L.tw2);
 #endif
     // ---- Makhoul post: k = s + 16 i, A = Z[k] = v[i], P = Z[M - k]
-#if DCTAE_T23
-    const auto rsrc = band ? __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(T) + (int64_t)c * H * KW * 3, 0,
-                                                               plane_bytes / 4 * 3, 0x00020000)
-                           : __builtin_amdgcn_make_buffer_rsrc(T + (int64_t)c * H * KW, 0, plane_bytes, 0x00020000);
-#else
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(T + (int64_t)c * H * KW, 0, plane_bytes, 0x00020000);
-#endif
 #if DCTAE_TLAYOUT == 2
     if constexpr (band) {
       // band16 layout [y / 16][kx][16 rows]: the block's 16 rows of a channel are
@@ -467,17 +392,10 @@ __device__ __forceinline__ void rows512_item_pk(Rows512XchPk& X, const Rows512Ta
       const int l = tid & 63;
       const int kx0 = 112 * wv + (l >> 2), qd = l & 3;   // + 16 it; (kx >> 1) & 3 = (l >> 3) & 3
       const float4* rd = reinterpret_cast<const float4*>(ob + kx0 * 16 + 4 * (qd ^ ((l >> 3) & 3)));
-#if DCTAE_T23
-      const int go = (((y0 >> 4) * KW + kx0) * 4 + qd) * 12;
-#pragma unroll
-      for (int it = 0; it < 7; ++it)
-        __builtin_amdgcn_raw_buffer_store_b96(t23_pack(rd[64 * it], qd), rsrc, go, 768 * it, DCTAE_T_ST_AUX);
-#else
       const int go = (((y0 >> 4) * KW + kx0) * 4 + qd) * 16;
 #pragma unroll
       for (int it = 0; it < 7; ++it)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, rd[64 * it]), rsrc, go, 1024 * it, DCTAE_T_ST_AUX);
-#endif
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, rd[64 * it]), rsrc, go, 1024 * it, kTStAux);
       __builtin_amdgcn_sched_barrier(0);   // keep the next channel's inputs from being built up here
     } else
 #endif

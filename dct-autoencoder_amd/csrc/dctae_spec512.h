@@ -67,9 +67,6 @@ __device__ __forceinline__ int64_t cols_tok(const ImgDesc& d, int c, int strip, 
 // 14 are the 196 contiguous floats Xf[196 h ..], the token's staged layout, so
 // the whole block stores them as 16-byte pieces (49 per token) instead of 14
 // scattered 4-byte stores per lane
-#ifndef DCTAE_TOK_ST_NT
-#define DCTAE_TOK_ST_NT 1
-#endif
 typedef float tok4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void cols_store_tokens(const ImgDesc& d, int c, int strip, const float* Xf, float* dst,
                                                   int C) {
@@ -78,13 +75,8 @@ __device__ __forceinline__ void cols_store_tokens(const ImgDesc& d, int c, int s
     const int h = e / 49, q = e - h * 49;
     // write-once staging (the projection kernel reads it later, 196 floats a
     // token): nontemporal, as T'
-#if DCTAE_TOK_ST_NT
     __builtin_nontemporal_store(reinterpret_cast<const tok4v*>(Xf + KS * KS * h)[q],
                                 reinterpret_cast<tok4v*>(dst + cols_tok(d, c, strip, h, C) * (KS * KS)) + q);
-#else
-    reinterpret_cast<float4*>(dst + cols_tok(d, c, strip, h, C) * (KS * KS))[q] =
-        reinterpret_cast<const float4*>(Xf + KS * KS * h)[q];
-#endif
   }
 }
 
@@ -429,61 +421,34 @@ struct Cols512bLds {
   float4 pc[256];               // c1..c4 of the Makhoul post, k < M (k = M in registers)
 };                              // 40,960 B: 4 blocks per CU
 
-// the band T' of one column as loaded (float4 of 4 rows, or with DCTAE_T23 the
-// 12-byte record quarter, decoded by t_decode when the transform starts)
-#if DCTAE_T23
-typedef v3u TPiece;
-#else
-typedef float4 TPiece;
-#endif
-__device__ __forceinline__ void t_decode(const TPiece (&q)[8], float4 (&f)[8]) {
-#if DCTAE_T23
-  const int j = opaque_tid() & 15;
-#pragma unroll
-  for (int b = 0; b < 8; ++b) f[b] = t23_unpack(q[b], j & 3);
-#else
+// the transform's inputs: a copy of the loaded pieces (as a function: written
+// out in the callers, or with the pieces passed on directly, the compiler
+// orders the operands of the FFT's packed adds differently)
+__device__ __forceinline__ void t_decode(const float4 (&q)[8], float4 (&f)[8]) {
 #pragma unroll
   for (int b = 0; b < 8; ++b) f[b] = q[b];
-#endif
 }
-__device__ __forceinline__ void t_opaque(TPiece (&q)[8]) {   // the loads become opaque values here
+__device__ __forceinline__ void t_opaque(float4 (&q)[8]) {   // the loads become opaque values here
 #pragma unroll
-  for (int r = 0; r < 8; ++r) {
-#if DCTAE_T23
-    asm volatile("" : "+v"(q[r].x), "+v"(q[r].y), "+v"(q[r].z));
-#else
+  for (int r = 0; r < 8; ++r)
     asm volatile("" : "+v"(q[r].x), "+v"(q[r].y), "+v"(q[r].z), "+v"(q[r].w));
-#endif
-  }
 }
-// lane j of column kx loads band4 = 16 b + j: record (band16 4 b + j / 4, kx), slot j % 4
-__device__ __forceinline__ void t_load_column(int c, int kx, int j, const float* __restrict__ T, TPiece (&q)[8]) {
+// lane j of column kx loads band4 = 16 b + j: band16 4 b + j / 4, slot j % 4
+__device__ __forceinline__ void t_load_column(int c, int kx, int j, const float* __restrict__ T, float4 (&q)[8]) {
   constexpr int KW = 448;
-#if DCTAE_T23
-  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(T)) +
-                                                          (int64_t)c * 512 * KW * 3, 0, 512 * KW * 3, 0x00020000);
-  const int o = (((j >> 2) * KW + kx) * 4 + (j & 3)) * 12;
-  constexpr int bstep = 4 * KW * 4 * 12;
-#pragma unroll
-  for (int b = 0; b < 8; ++b) q[b] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, o, b * bstep, DCTAE_T_LD_AUX);
-#else
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(T) + (int64_t)c * 512 * KW, 0, 512 * KW * 4,
                                                       0x00020000);
   const int o = t4_index(j, kx) * 16;   // band4 = 16 b + j
   constexpr int bstep = 16 * KW * 16;   // t4_index(16 b + j, kx) - t4_index(16 (b - 1) + j, kx), both layouts
 #pragma unroll
   for (int b = 0; b < 8; ++b)
-    q[b] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, b * bstep, DCTAE_T_LD_AUX));
-#endif
+    q[b] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, b * bstep, kTLdAux));
 }
 
-__device__ __forceinline__ void cols512b_load(int c, int strip, const float* __restrict__ T, TPiece (&q)[8]) {
+__device__ __forceinline__ void cols512b_load(int c, int strip, const float* __restrict__ T, float4 (&q)[8]) {
   const int tid = opaque_tid();
   const int G = tid >> 4, j = tid & 15;
   constexpr int KW = 448;
-#if DCTAE_T23
-  t_load_column(c, 14 * strip + min(G, 13), j, T, q);
-#else
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(T) + (int64_t)c * 512 * KW, 0, 512 * KW * 4,
                                                       0x00020000);
   const int kx = 14 * strip + min(G, 13);
@@ -498,8 +463,7 @@ __device__ __forceinline__ void cols512b_load(int c, int strip, const float* __r
 #endif
 #pragma unroll
   for (int b = 0; b < 8; ++b)
-    q[b] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, b * bstep, DCTAE_T_LD_AUX));
-#endif
+    q[b] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, b * bstep, kTLdAux));
 }
 
 // PatchNorm-output epilogue of k_cols512b (the LFQ-projection encode's staged

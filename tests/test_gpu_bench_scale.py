@@ -149,7 +149,7 @@ def test_config4_full_batch_vs_oracle_and_small_batch(setup, ref_tables):
 
 def test_config4_run_to_run_identical(setup):
     """The config-4 batch encodes bit-identically call after call (40 calls,
-    raw tokens and codes).  k_rows_fused's interleaved form (DCTAE_FUSED_PIPE)
+    raw tokens and codes).  k_rows_fused's removed interleaved form
     differed from the previous call on 3-6 % of calls here, always in whole
     low-kx coefficient columns of the first images (tools/c4_stress.py); the
     two-call parity test above saw it only about once per four suites."""
