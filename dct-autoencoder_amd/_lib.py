@@ -91,6 +91,11 @@ _SIGS = {
                            C.c_int),
     "dctae_lfq_forward": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, _P, _P, _P], C.c_int),
     "dctae_lfq_indices_to_codes": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, _P, _P], C.c_int),
+    "dctae_lfq_entropy_forward": ([_P, C.POINTER(LFQCfg), _P, _P, C.c_int64, C.c_float, C.c_float, _P, _P, _P],
+                                  C.c_int),
+    "dctae_lfq_entropy_backward": ([_P, C.POINTER(LFQCfg), _P, _P, C.c_int64, C.c_float, C.c_float, _P, _P, _P, _P,
+                                    _P], C.c_int),
+    "dctae_linear_ordered": ([_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int32, _P, _P], C.c_int),
     "dctae_lfq_project_in": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, C.c_int32, _P, _P, _P, _P], C.c_int),
     "dctae_lfq_project_in_bounded": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, C.c_int32, _P, _P, C.c_float, _P, _P],
                                      C.c_int),

@@ -278,6 +278,74 @@ def lfq_forward(x: torch.Tensor, cfg: LFQCfg, want_quantized=True):
     return q, idx
 
 
+def _lfq_entropy_args(h: torch.Tensor, mask: torch.Tensor, cfg: LFQCfg):
+    dev = _check_dev(h, mask)
+    if cfg.codebook_dim > 16 or cfg.num_codebooks > 32:
+        raise NotImplementedError("the fused LFQ entropy loss serves codebook_dim <= 16 and num_codebooks <= 32 "
+                                  f"(got {cfg.codebook_dim}, {cfg.num_codebooks})")
+    d = cfg.codebook_dim * cfg.num_codebooks
+    hs = h.detach().float().contiguous()
+    if hs.numel() % d:
+        raise AssertionError(f"{hs.numel()} features are no whole number of tokens of dimension {d}")
+    n = hs.numel() // d
+    if mask.numel() != n:
+        raise AssertionError(f"mask of {mask.numel()} entries for {n} tokens")
+    ms = mask.to(torch.bool).contiguous().view(torch.uint8)
+    return dev, hs, ms, n
+
+
+def lfq_entropy_forward(h: torch.Tensor, mask: torch.Tensor, cfg: LFQCfg, temperature=0.01, eps=1e-9):
+    """The LFQ training losses of projected features h (..., num_codebooks *
+    codebook_dim) without the dense distance tensor (dctae_lfq_entropy_forward).
+    mask (...): True at real tokens.  Returns avg_probs (2**codebook_dim) and
+    scalars (5) = [entropy loss, sample_entropy, avg_entropy, commit_loss, M],
+    fp32 on h's device."""
+    dev, hs, ms, n = _lfq_entropy_args(h, mask, cfg)
+    ctx = _lib.context(dev)
+    avg = torch.empty(2 ** cfg.codebook_dim, dtype=torch.float32, device=dev)
+    sc = torch.empty(5, dtype=torch.float32, device=dev)
+    rc = ctx.lib.dctae_lfq_entropy_forward(ctx.h, C.byref(cfg), ptr(hs), ptr(ms), n, float(temperature), float(eps),
+                                           ptr(avg), ptr(sc), _lib.stream_ptr(dev))
+    ctx.check(rc, "dctae_lfq_entropy_forward")
+    return avg, sc
+
+
+def lfq_entropy_backward(h: torch.Tensor, mask: torch.Tensor, cfg: LFQCfg, avg: torch.Tensor, sc: torch.Tensor,
+                         grad: torch.Tensor, temperature=0.01, eps=1e-9) -> torch.Tensor:
+    """grad * d(entropy loss) / dh, fp32, h's shape; exact zeros at masked-out
+    tokens.  avg / sc: lfq_entropy_forward's outputs for the same arguments;
+    grad: the upstream gradient, a scalar tensor on the device."""
+    dev, hs, ms, n = _lfq_entropy_args(h, mask, cfg)
+    _check_dev(avg, sc, grad)
+    ctx = _lib.context(dev)
+    g = grad.detach().to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+    dh = torch.empty_like(hs)
+    rc = ctx.lib.dctae_lfq_entropy_backward(ctx.h, C.byref(cfg), ptr(hs), ptr(ms), n, float(temperature), float(eps),
+                                            ptr(avg), ptr(sc), ptr(g), ptr(dh), _lib.stream_ptr(dev))
+    ctx.check(rc, "dctae_lfq_entropy_backward")
+    return dh
+
+
+def linear_ordered(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
+    """x (..., K) w (D, K)^T + b with every output summed over k in index
+    order, bias last (dctae_linear_ordered); fp32, no autograd."""
+    dev = _check_dev(x, w, b)
+    ctx = _lib.context(dev)
+    xs = x.detach().float().contiguous()
+    K = xs.shape[-1]
+    if w.shape[1] != K:
+        raise AssertionError(f"expected dimension of {w.shape[1]} but received {K}")
+    if K > 512:
+        raise NotImplementedError("ordered linear: at most 512 input features")
+    wt = w.detach().float().t().contiguous()
+    bs = None if b is None else b.detach().float().contiguous()
+    out = torch.empty((*xs.shape[:-1], w.shape[0]), dtype=torch.float32, device=dev)
+    rc = ctx.lib.dctae_linear_ordered(ctx.h, ptr(xs), xs.numel() // K, K, ptr(wt), ptr(bs), w.shape[0], ptr(out),
+                                      _lib.stream_ptr(dev))
+    ctx.check(rc, "dctae_linear_ordered")
+    return out
+
+
 def lfq_codes(idx: torch.Tensor, cfg: LFQCfg) -> torch.Tensor:
     dev = _check_dev(idx)
     ctx = _lib.context(dev)

@@ -2181,6 +2181,70 @@ int dctae_lfq_indices_to_codes(dctae_ctx* ctx, const dctae_lfq* lfq, const int64
   return 0;
 }
 
+static int lfq_entropy_check(dctae_ctx* ctx, const dctae_lfq* lfq, const void* h, const void* mask, int64_t n_tok,
+                             float temperature) {
+  if (!lfq || lfq->codebook_dim < 1 || lfq->num_codebooks < 1 || n_tok < 0)
+    return fail(ctx, DCTAE_EINVAL, "bad LFQ config");
+  if (!lfq_entropy_supported(lfq->codebook_dim, lfq->num_codebooks, n_tok))
+    return fail(ctx, DCTAE_EUNSUP, "LFQ entropy loss: codebook_dim <= 16 and num_codebooks <= 32");
+  if (n_tok > 0 && (!h || !mask)) return fail(ctx, DCTAE_EINVAL, "bad LFQ tensors");
+  if (!(temperature != 0.0f)) return fail(ctx, DCTAE_EINVAL, "temperature must not be 0");
+  return 0;
+}
+
+int dctae_lfq_entropy_forward(dctae_ctx* ctx, const dctae_lfq* lfq, const float* h, const uint8_t* mask,
+                              int64_t n_tok, float temperature, float eps, float* avg_probs, float* scalars,
+                              void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  int rc;
+  if ((rc = lfq_entropy_check(ctx, lfq, h, mask, n_tok, temperature))) return rc;
+  if (!avg_probs || !scalars) return fail(ctx, DCTAE_EINVAL, "NULL output");
+  if ((rc = ensure_ws(ctx, sizeof(float) * lfq_entropy_fwd_ws_floats(n_tok, lfq->num_codebooks, lfq->codebook_dim),
+                      256)))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "lfq_entropy_forward");
+  launch_lfq_entropy_fwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature, eps,
+                         ctx->ws, avg_probs, scalars, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_lfq_entropy_backward(dctae_ctx* ctx, const dctae_lfq* lfq, const float* h, const uint8_t* mask,
+                               int64_t n_tok, float temperature, float eps, const float* avg_probs,
+                               const float* scalars, const float* grad, float* dh, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  int rc;
+  if ((rc = lfq_entropy_check(ctx, lfq, h, mask, n_tok, temperature))) return rc;
+  if (!avg_probs || !scalars || !grad || (n_tok > 0 && !dh)) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  if (n_tok == 0) return 0;
+  if ((rc = ensure_ws(ctx, sizeof(float) * lfq_entropy_bwd_ws_floats(lfq->codebook_dim), 256))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "lfq_entropy_backward");
+  if (launch_lfq_entropy_bwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature,
+                             eps, avg_probs, scalars, grad, ctx->ws, dh, s))
+    return fail(ctx, DCTAE_EHIP, "LFQ entropy backward: the kernel's LDS size could not be set");
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_linear_ordered(dctae_ctx* ctx, const float* x, int64_t n, int32_t K, const float* wt, const float* b,
+                         int32_t dim, float* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  if (n < 0 || K < 1 || dim < 1 || n / 16 >= (int64_t)INT32_MAX) return fail(ctx, DCTAE_EINVAL, "bad linear shape");
+  if (!linear_ordered_supported(K, dim)) return fail(ctx, DCTAE_EUNSUP, "ordered linear: K <= 512");
+  if (n == 0) return 0;
+  if (!x || !wt || !out) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "linear_ordered");
+  launch_linear_ordered(x, n, K, wt, b, dim, out, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
 static int lfq_proj_check(dctae_ctx* ctx, const dctae_lfq* lfq, int64_t n, int32_t dim, const void* a,
                           const float* w, const void* o, int max_ncb, bool o_vec = false) {
   if (!lfq || lfq->codebook_dim < 1 || lfq->codebook_dim > 31 || lfq->num_codebooks < 1 ||

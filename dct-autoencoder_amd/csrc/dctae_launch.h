@@ -74,6 +74,21 @@ void launch_lfq_ws(int mode, hipStream_t s, const float* x, const int64_t* idx_i
                    const float* bias, int cd, int ncb, float scale, int64_t* idx_out, float* out, uint16_t* idx16,
                    const int64_t* ch, const int64_t* pos, const float* med, const float* nb, float eps, int maxph,
                    int maxpw, int* err, const uint16_t* wsp, int NPw, int Kp, float a_scale);
+// dctae_lfq_entropy.hip: LFQ training losses (entropy + commit) and the entropy loss's gradient
+bool lfq_entropy_supported(int d, int c, int64_t n_tok);
+size_t lfq_entropy_fwd_ws_floats(int64_t n_tok, int c, int d);
+// out[0..4] = entropy loss, sample_entropy, avg_entropy, commit_loss, M; avg: 2^d floats
+void launch_lfq_entropy_fwd(const float* h, const uint8_t* mask, int64_t n_tok, int c, int d, float s, float T,
+                            float eps, float* ws, float* avg, float* out, hipStream_t st);
+size_t lfq_entropy_bwd_ws_floats(int d);
+// gup: the upstream gradient of the entropy loss (device scalar); nonzero: the LDS size could not be set
+int launch_lfq_entropy_bwd(const float* h, const uint8_t* mask, int64_t n_tok, int c, int d, float s, float T,
+                           float eps, const float* avg, const float* out, const float* gup, float* ws, float* dh,
+                           hipStream_t st);
+// out (n, D) = x (n, K) w^T + b, each output one fmaf chain over k ascending, bias last; wt = w^T (K, D)
+bool linear_ordered_supported(int K, int D);
+void launch_linear_ordered(const float* x, int64_t n, int K, const float* wt, const float* b, int D, float* out,
+                           hipStream_t st);
 // VectorQuantize inference (dctae_vq.hip)
 void launch_vq_bias(float* y, const float* bias, int64_t n, int cols, const uint8_t* mask, const float* orig,
                     hipStream_t s);

@@ -10,8 +10,23 @@ kernels (dctae_lfq_project_in: project_in + sign + packing, the projected
 features never stored; dctae_lfq_project_out: index bits -> +-scale codes ->
 project_out).  The module's nn.Linear weights stay the parameters (state dicts
 interchange with the reference); the kernels read fp32 copies of them.
-The training-only losses (commit / entropy, lfq.py:189-204) are out of scope
-of this build.
+
+Training mode (lfq.py:164-204): ``project_in`` runs as the module's own
+nn.Linear and ``project_out`` as the same linear map of the module's weight
+and bias with its forward summed in a fixed order (dctae_linear_ordered; both
+get nn.Linear's gradients), indices and quantized
+values come from dctae_lfq_forward, the output is the straight-through
+``activation(h) - activation(h).detach() + quantized`` and ``commit_loss``
+comes from the fused loss kernel (dctae_lfq_entropy_forward; its gradient is
+element-wise torch).  The fourth return value is an ``LFQDistance``
+(losses.py) in place of the reference's dense (b, n, c, 2**codebook_dim)
+distance tensor: ``losses.compute_entropy_loss`` takes it and runs the fused
+HIP entropy loss and gradient on the projected features alone;
+``.materialize()`` builds the dense tensor where one is wanted.  Values of
+masked-out tokens are never read by the fused losses (the reference multiplies
+them by 0, so a NaN in padding poisons its losses; here it does not).  The
+fused losses serve codebook_dim <= 16 and num_codebooks <= 32; beyond that the
+training forward raises NotImplementedError.
 """
 from __future__ import annotations
 
@@ -22,12 +37,29 @@ import torch
 from einops import rearrange
 from torch import nn
 
-from . import _ops
+from . import _ops, losses
 from ._lib import LFQCfg
 
 
 def _exists(v):
     return v is not None
+
+
+class _OrderedLinear(torch.autograd.Function):
+    """F.linear with the forward on dctae_linear_ordered (fixed summation
+    order); the backward is F.linear's."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        return _ops.linear_ordered(x, w, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        g2, x2 = g.reshape(-1, g.shape[-1]), x.reshape(-1, x.shape[-1])
+        return g @ w, g2.t() @ x2, (g2.sum(0) if ctx.has_bias else None)
 
 
 class LFQ(nn.Module):
@@ -131,12 +163,13 @@ class LFQ(nn.Module):
         return codes
 
     def forward(self, x, mask=None):
-        """lfq.py:136-227 (eval).  ``mask`` (False at padding) is required, as
-        in the reference, and unused in eval."""
+        """lfq.py:136-227.  ``mask`` (False at padding) is required, as in the
+        reference; eval does not use it.  Training returns (x_q, indices,
+        commit_loss, LFQDistance); see the module docstring."""
         if mask is None:
             raise NotImplementedError("mask")
         if self.training:
-            raise NotImplementedError("LFQ training losses (lfq.py:189-204) are out of scope of the MI355X path")
+            return self._forward_train(x, mask)
         is_img_or_video = x.ndim >= 4
         if is_img_or_video:
             x = rearrange(x, "b d ... -> b ... d")
@@ -165,3 +198,44 @@ class LFQ(nn.Module):
         if not self.keep_num_codebooks_dim:
             indices = rearrange(indices, "... 1 -> ...")
         return q, indices, self.zero, self.zero
+
+    def _forward_train(self, x, mask):
+        """lfq.py:151-227 with self.training"""
+        if self.codebook_dim > 16 or self.num_codebooks > 32:
+            raise NotImplementedError("LFQ training: the fused losses serve codebook_dim <= 16 and "
+                                      f"num_codebooks <= 32 (got {self.codebook_dim}, {self.num_codebooks})")
+        is_img_or_video = x.ndim >= 4
+        if is_img_or_video:
+            x = rearrange(x, "b d ... -> b ... d")
+            shape = x.shape
+            x = x.reshape(shape[0], -1, shape[-1])
+        assert x.shape[-1] == self.dim, f"expected dimension of {self.dim} but received {x.shape[-1]}"
+        h = self.project_in(x)
+        q, indices = _ops.lfq_forward(h, self.cfg(h.dtype))
+        a = self.activation(h)
+        xq = a - a.detach() + q.to(h.dtype)
+        h4 = h.view(*h.shape[:-1], self.num_codebooks, self.codebook_dim)
+        dist = losses.LFQDistance(h4, self.codebook_scale, self.codebook_dim, self.num_codebooks)
+        commit_loss = losses.commit_loss(dist, mask)
+        xq = self._project_out_train(xq)
+        if is_img_or_video:
+            xq = xq.reshape(*shape[:-1], xq.shape[-1])
+            xq = rearrange(xq, "b ... d -> b d ...")
+            indices = indices.reshape(*shape[:-1], indices.shape[-1])
+        if not self.keep_num_codebooks_dim:
+            indices = rearrange(indices, "... 1 -> ...")
+        return xq, indices, commit_loss, dist
+
+    def _project_out_train(self, xq):
+        """project_out of the training forward.  fp32: the module's weight and
+        bias through ``_OrderedLinear`` -- every output summed over its inputs
+        in index order, bias last, so x_q does not depend on a GEMM library's
+        blocking (it equals the reference's CPU result bit for bit where that
+        GEMM sums in the same plain order); the gradients of input, weight and
+        bias are nn.Linear's.  Other dtypes: nn.Linear in the model dtype."""
+        if not self.has_projections:
+            return xq
+        lin = self.project_out
+        if xq.dtype != torch.float32 or lin.weight.dtype != torch.float32:
+            return lin(xq)
+        return _OrderedLinear.apply(xq, lin.weight, lin.bias)

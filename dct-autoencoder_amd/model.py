@@ -22,9 +22,11 @@ id equals the key's and the key is padding, FE:580-584) and nothing is masked
 ``batched_image_ids`` / ``key_pad_mask``, which is how the feature extractor
 defines it.
 
-Training (losses, backward, the VectorQuantize variant's codebook updates) is
-not on the MI355X path: ``encode`` / ``decode`` in training mode raise
-NotImplementedError.
+The transformer has no backward here (nor the VectorQuantize variant its
+codebook updates): ``encode`` / ``decode`` in training mode raise
+NotImplementedError.  The quantizer's training losses are on the MI355X path:
+``self.vq_model`` (LFQ) runs in ``.train()`` on its own, and ``entropy_loss``
+(modeling:196-200) takes the ``LFQDistance`` it returns.
 """
 from __future__ import annotations
 
@@ -38,6 +40,7 @@ from torch import nn
 from . import _lib
 from .dct_patches import DCTPatches
 from .lfq import LFQ
+from .losses import compute_entropy_loss
 from .patchnorm import PatchNorm
 
 
@@ -224,6 +227,15 @@ class DCTAutoencoder(nn.Module):
     def inv_normalize_(self, x: DCTPatches):
         x.patches = self.patchnorm.inverse_norm(x)
         return x
+
+    def entropy_loss(self, distances, mask):
+        """modeling:196-200.  distances: the fourth return value of the
+        quantizer's training forward (an ``LFQDistance``: the fused HIP loss
+        and gradient) or a dense tensor (evaluated in fp32 with torch ops)."""
+        if torch.is_tensor(distances):
+            og_dtype = distances.dtype
+            return compute_entropy_loss(distances.float(), mask).to(og_dtype)
+        return compute_entropy_loss(distances, mask)
 
     # ---- plumbing ----
     @staticmethod

@@ -211,6 +211,43 @@ int dctae_lfq_forward(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x_dev, 
 int dctae_lfq_indices_to_codes(dctae_ctx* ctx, const dctae_lfq* lfq, const int64_t* indices_dev,
                                int64_t n, float* codes_dev, void* stream);
 
+/* LFQ.forward training losses without the dense distance tensor: the commit
+ * loss (lfq.py:195-200) and compute_entropy_loss (util.py:355-387) of
+ * distance = -2 einsum(h, codebook) (lfq.py:191), from the projected features
+ * h (n_tok, num_codebooks * codebook_dim) fp32 alone -- the codebook is
+ * {-s, +s}^d, so the softmax over the codes factorises over the bits and
+ * avg_probs is one exact-fp32 MFMA GEMM.  mask_dev (n_tok) u8: nonzero at real
+ * tokens; values of masked-out tokens are never read (the reference multiplies
+ * them by 0, so a NaN there poisons its loss; here it does not).
+ * avg_probs_dev: 2^codebook_dim floats.  scalars_dev: 5 floats = entropy loss
+ * (sample_entropy - avg_entropy), sample_entropy, avg_entropy, commit_loss, M
+ * (masked-in tokens; M = 0 gives NaN losses, as the reference).  Bit-identical
+ * from run to run.  codebook_dim <= 16 and num_codebooks <= 32, else
+ * DCTAE_EUNSUP. */
+int dctae_lfq_entropy_forward(dctae_ctx* ctx, const dctae_lfq* lfq, const float* h_dev, const uint8_t* mask_dev,
+                              int64_t n_tok, float temperature, float eps, float* avg_probs_dev,
+                              float* scalars_dev, void* stream);
+
+/* Gradient of that entropy loss: dh (n_tok, num_codebooks * codebook_dim) =
+ * grad * d(entropy loss) / dh, exact zeros at masked-out tokens.  avg_probs_dev
+ * and scalars_dev: the forward's outputs for the same h, mask, temperature and
+ * eps; grad_dev: the upstream gradient, one fp32 on the device (nothing
+ * synchronises).  Same limits as the forward. */
+int dctae_lfq_entropy_backward(dctae_ctx* ctx, const dctae_lfq* lfq, const float* h_dev, const uint8_t* mask_dev,
+                               int64_t n_tok, float temperature, float eps, const float* avg_probs_dev,
+                               const float* scalars_dev, const float* grad_dev, float* dh_dev, void* stream);
+
+/* LFQ.forward training, project_out (lfq.py:212) in a fixed summation order:
+ * out (n, dim) = x (n, K) w^T + b with every output the fp32 sum of its K
+ * terms in index order (one fused multiply-add per term, starting from 0), the
+ * bias added last -- the order of a plain loop, independent of any GEMM
+ * library's blocking, so the straight-through output is the same on every
+ * device.  wt_dev: the weight TRANSPOSED, (K, dim) contiguous; b_dev (dim,
+ * nullable).  K <= 512 (num_codebooks * codebook_dim of the training limits),
+ * else DCTAE_EUNSUP. */
+int dctae_linear_ordered(dctae_ctx* ctx, const float* x_dev, int64_t n, int32_t K, const float* wt_dev,
+                         const float* b_dev, int32_t dim, float* out_dev, void* stream);
+
 /* dctae_encode for an LFQ with projections (lfq.py:54-62; conf/patch14-l.json:
  * 196 -> 16 x 13): the column epilogues stage the PatchNorm output, the fused
  * project_in + sign + pack kernel (below) turns the staged tokens into staged
