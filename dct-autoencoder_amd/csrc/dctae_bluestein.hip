@@ -229,7 +229,8 @@ __global__ __launch_bounds__(Bs<L>::NT) void k_bs_rows(const ImgDesc* __restrict
                                                  int ablate) {
   using S = Bs<L>;
   constexpr int PXI = (L / 2 + S::NT - 1) / S::NT, NR = 2 * S::G;
-  constexpr int KI = ((L / 2 < 448 ? L / 2 : 448) + S::NT - 1) / S::NT;
+  // kept coefficients per thread: Kw <= W = N <= L / 2 (any patch size / max_patch_w)
+  constexpr int KI = (L / 2 + S::NT - 1) / S::NT;
   __shared__ float2 lds[S::JOBS * S::LP];
   const int2 jb = blocks[blockIdx.x];
   const ImgDesc d = imgs[jb.x];
@@ -324,7 +325,9 @@ __global__ __launch_bounds__(Bs<L>::NT) void k_bs_cols(const ImgDesc* __restrict
   // N * NC <= (L / 2) * 6 * 128 * 16 / L = 16 * NT: sixteen loads per thread
   constexpr int EI = (L / 2 * NC + S::NT - 1) / S::NT;
   constexpr int KPR = S::NT / S::JOBS;
-  constexpr int KR = ((L / 2 < 448 ? L / 2 : 448) + KPR - 1) / KPR;
+  // kept rows per thread: Kh <= H = N <= L / 2.  (A bound of 448 = 14 x 32 rows here left
+  // rows 448.. of Y unwritten at patch sizes 15 / 16 or max_patch_h > 32 on sides above 448.)
+  constexpr int KR = (L / 2 + KPR - 1) / KPR;
   __shared__ float2 lds[S::JOBS * S::LP];
   const int4 jb = blocks[blockIdx.x];
   const ImgDesc d = imgs[jb.x];

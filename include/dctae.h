@@ -46,7 +46,7 @@ typedef struct dctae_ctx dctae_ctx;
 /* DCTAutoencoderFeatureExtractor.__init__ arguments (FE:108-127). */
 typedef struct {
   int32_t channels;               /* must be 3 (IPT colour transform, util.py:70-97) */
-  int32_t patch_size;             /* P, 2..16 (reference configs use 14) */
+  int32_t patch_size;             /* P, 1..16 (reference configs use 14) */
   int32_t max_patch_h;            /* 32 */
   int32_t max_patch_w;            /* 32 */
   int32_t max_seq_len;            /* S */
