@@ -1,0 +1,647 @@
+// C ABI entry points of the single operators: PatchNorm and its statistics,
+// LFQ (entropy and projections included), VectorQuantize and the transformer
+// operators of dctae_model.hip.
+#include "dctae_ctx.h"
+#include "dctae_model.h"
+
+using namespace dctae;
+
+extern "C" {
+
+int dctae_norm_thresholds(dctae_ctx* ctx, const dctae_norm* norm, int64_t n, float* thr_dev, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (!norm || !norm->median_dev || !norm->b_dev || !thr_dev || n < 0)
+    return fail(ctx, DCTAE_EINVAL, "bad threshold arguments");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(ctx, hipMemsetAsync(ctx->err_dev, 0, sizeof(int), s));
+  launch_norm_thresholds(norm->median_dev, norm->b_dev, n, norm->eps, norm->min_val, norm->max_val, thr_dev,
+                         ctx->err_dev, s);
+  HIPCHK(ctx, hipGetLastError());
+  int h = 0;
+  HIPCHK(ctx, hipMemcpyAsync(&h, ctx->err_dev, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  HIPCHK(ctx, hipMemsetAsync(ctx->err_dev, 0, sizeof(int), s));
+  if (h) return fail(ctx, DCTAE_EUNSUP, "negative PatchNorm std: thresholds undefined (use thr_dev = NULL)");
+  return 0;
+}
+
+static int norm_impl(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t mh, int32_t mw, const float* x,
+                     const int64_t* ch, const int64_t* pos, int64_t n, float* y, int inverse, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (!norm || !norm->median_dev || !norm->b_dev) return fail(ctx, DCTAE_EINVAL, "PatchNorm tables are NULL");
+  if (P < 1 || mh < 1 || mw < 1 || n < 0) return fail(ctx, DCTAE_EINVAL, "bad PatchNorm shape");
+  if (n == 0) return 0;
+  if (!x || !ch || !pos || !y) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, inverse ? "norm_inverse" : "norm_forward");
+  launch_norm(x, ch, pos, n, P * P, mh, mw, norm->median_dev, norm->b_dev, norm->eps, norm->min_val, norm->max_val,
+              inverse, y, ctx->err_dev, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_norm_forward(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t mh, int32_t mw, const float* x,
+                       const int64_t* ch, const int64_t* pos, int64_t n, float* y, void* stream) {
+  return norm_impl(ctx, norm, P, mh, mw, x, ch, pos, n, y, 0, stream);
+}
+
+int dctae_norm_inverse(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t mh, int32_t mw, const float* y,
+                       const int64_t* ch, const int64_t* pos, int64_t n, float* x, void* stream) {
+  return norm_impl(ctx, norm, P, mh, mw, y, ch, pos, n, x, 1, stream);
+}
+
+// ---- PatchNorm training (patchnorm.py:101-155), kernels in dctae_stats.hip ----
+namespace {
+
+struct StatsScratch {
+  int32_t *cell, *count, *start, *list;
+  float* bn;       // (n_cells) batch counts
+  float *t0, *t1;  // two (n_cells, PP) tables (batch median / batch b)
+};
+
+int stats_scratch(dctae_ctx* ctx, int64_t n_tok, int n_cells, int PP, bool tables, hipStream_t s,
+                  StatsScratch* o) {
+  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t b_tok = al(sizeof(int32_t) * std::max<int64_t>(n_tok, 1));
+  const size_t b_cell = al(sizeof(int32_t) * n_cells);
+  const size_t b_tab = tables ? al(sizeof(float) * (size_t)n_cells * PP) : 0;
+  const size_t need = 2 * b_tok + 3 * b_cell + 2 * b_tab;
+  if (need > ctx->st_bytes) {
+    if (ctx->st_ws) {
+      HIPCHK(ctx, hipStreamSynchronize(s));
+      HIPCHK(ctx, hipFree(ctx->st_ws));
+      ctx->st_ws = nullptr;
+      ctx->st_bytes = 0;
+    }
+    HIPCHK(ctx, hipMalloc((void**)&ctx->st_ws, need));
+    ctx->st_bytes = need;
+  }
+  uint8_t* p = ctx->st_ws;
+  o->cell = (int32_t*)p;
+  p += b_tok;
+  o->list = (int32_t*)p;
+  p += b_tok;
+  o->count = (int32_t*)p;
+  p += b_cell;
+  o->start = (int32_t*)p;
+  p += b_cell;
+  o->bn = (float*)p;
+  p += b_cell;
+  o->t0 = tables ? (float*)p : nullptr;
+  p += b_tab;
+  o->t1 = tables ? (float*)p : nullptr;
+  return 0;
+}
+
+int stats_check(dctae_ctx* ctx, int32_t P, int32_t C, int32_t mh, int32_t mw, int64_t n_tok, const float* x,
+                const int64_t* ch, const int64_t* pos) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (P < 1 || C < 1 || mh < 1 || mw < 1 || n_tok < 0) return fail(ctx, DCTAE_EINVAL, "bad PatchNorm shape");
+  if ((int64_t)C * mh * mw > (1 << 30)) return fail(ctx, DCTAE_EINVAL, "PatchNorm table too large");
+  if (n_tok > (int64_t)INT32_MAX) return fail(ctx, DCTAE_EINVAL, "too many tokens for one statistics batch");
+  if (n_tok > 0 && (!x || !ch || !pos)) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  return 0;
+}
+
+}  // namespace
+
+int dctae_norm_batch_stats(dctae_ctx* ctx, int32_t P, int32_t C, int32_t mh, int32_t mw, const float* x,
+                           const int64_t* ch, const int64_t* pos, const uint8_t* key_pad, int64_t n_tok,
+                           float* batch_n, float* batch_median, void* stream) {
+  if (int rc = stats_check(ctx, P, C, mh, mw, n_tok, x, ch, pos)) return rc;
+  if (!batch_n || !batch_median) return fail(ctx, DCTAE_EINVAL, "NULL output table");
+  hipStream_t s = (hipStream_t)stream;
+  const int n_cells = C * mh * mw, PP = P * P;
+  StatsScratch w;
+  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, false, s, &w)) return rc;
+  Timer t(ctx, s, "norm_batch_stats");
+  launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
+  launch_stats_median(x, PP, n_cells, w.start, w.count, w.list, batch_median, batch_n, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_norm_batch_mad(dctae_ctx* ctx, int32_t P, int32_t C, int32_t mh, int32_t mw, const float* x,
+                         const int64_t* ch, const int64_t* pos, const uint8_t* key_pad, int64_t n_tok,
+                         const float* median, float* batch_b, void* stream) {
+  if (int rc = stats_check(ctx, P, C, mh, mw, n_tok, x, ch, pos)) return rc;
+  if (!median || !batch_b) return fail(ctx, DCTAE_EINVAL, "NULL table");
+  hipStream_t s = (hipStream_t)stream;
+  const int n_cells = C * mh * mw, PP = P * P;
+  StatsScratch w;
+  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, false, s, &w)) return rc;
+  Timer t(ctx, s, "norm_batch_mad");
+  launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
+  launch_stats_batch_b(x, PP, n_cells, w.start, w.count, w.list, median, batch_b, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_norm_merge(dctae_ctx* ctx, int32_t n_cells, int32_t PP, float* table, const float* batch, float* n,
+                     const float* batch_n, int32_t n_update, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (n_cells < 0 || PP < 1) return fail(ctx, DCTAE_EINVAL, "bad PatchNorm shape");
+  if (n_cells == 0) return 0;
+  if (!n || !batch_n || ((!table || !batch) && PP > 0)) return fail(ctx, DCTAE_EINVAL, "NULL table");
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "norm_merge");
+  launch_stats_merge(table, batch, n, batch_n, n_cells, PP, s);
+  if (n_update) launch_stats_add(n, batch_n, n_cells, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_norm_train_step(dctae_ctx* ctx, const dctae_norm* norm, float* n_dev, int32_t P, int32_t C, int32_t mh,
+                          int32_t mw, const float* x, const int64_t* ch, const int64_t* pos, const uint8_t* key_pad,
+                          int64_t n_tok, float* y, void* stream) {
+  if (int rc = stats_check(ctx, P, C, mh, mw, n_tok, x, ch, pos)) return rc;
+  if (!norm || !norm->median_dev || !norm->b_dev || !n_dev) return fail(ctx, DCTAE_EINVAL, "PatchNorm tables are NULL");
+  hipStream_t s = (hipStream_t)stream;
+  const int n_cells = C * mh * mw, PP = P * P;
+  float* median = const_cast<float*>(norm->median_dev);
+  float* b = const_cast<float*>(norm->b_dev);
+  StatsScratch w;
+  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, true, s, &w)) return rc;
+  Timer t(ctx, s, "norm_train_step");
+  launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
+  launch_stats_median(x, PP, n_cells, w.start, w.count, w.list, w.t0, w.bn, s);      // :112-130
+  launch_stats_merge(median, w.t0, n_dev, w.bn, n_cells, PP, s);                     // :135-138
+  launch_stats_batch_b(x, PP, n_cells, w.start, w.count, w.list, median, w.t1, s);   // :140-144
+  launch_stats_merge(b, w.t1, n_dev, w.bn, n_cells, PP, s);                          // :146-148
+  launch_stats_add(n_dev, w.bn, n_cells, s);                                         // :150
+  if (y && n_tok > 0) {                                                              // :153-155
+    if (key_pad) launch_zero_pads(x, key_pad, n_tok, PP, y, s);
+    else if (y != x) HIPCHK(ctx, hipMemcpyAsync(y, x, sizeof(float) * n_tok * PP, hipMemcpyDeviceToDevice, s));
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_lfq_forward(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x, int64_t n, float* q, int64_t* idx,
+                      void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (!lfq || lfq->codebook_dim < 1 || lfq->codebook_dim > 62 || lfq->num_codebooks < 1)
+    return fail(ctx, DCTAE_EINVAL, "bad LFQ config");
+  if (n < 0 || (n > 0 && (!x || !idx))) return fail(ctx, DCTAE_EINVAL, "bad LFQ tensors");
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "lfq_forward");
+  launch_lfq_forward(x, n, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, q, idx, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_lfq_indices_to_codes(dctae_ctx* ctx, const dctae_lfq* lfq, const int64_t* idx, int64_t n, float* codes,
+                               void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (!lfq || lfq->codebook_dim < 1 || lfq->codebook_dim > 31 || lfq->num_codebooks < 1)
+    return fail(ctx, DCTAE_EINVAL, "bad LFQ config (codebook_dim <= 31: lfq.py:117 casts to int32)");
+  if (n < 0 || (n > 0 && (!idx || !codes))) return fail(ctx, DCTAE_EINVAL, "bad LFQ tensors");
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "lfq_codes");
+  launch_lfq_codes(idx, n, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, codes, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+static int lfq_entropy_check(dctae_ctx* ctx, const dctae_lfq* lfq, const void* h, const void* mask, int64_t n_tok,
+                             float temperature) {
+  if (!lfq || lfq->codebook_dim < 1 || lfq->num_codebooks < 1 || n_tok < 0)
+    return fail(ctx, DCTAE_EINVAL, "bad LFQ config");
+  if (!lfq_entropy_supported(lfq->codebook_dim, lfq->num_codebooks, n_tok))
+    return fail(ctx, DCTAE_EUNSUP, "LFQ entropy loss: codebook_dim <= 16 and num_codebooks <= 32");
+  if (n_tok > 0 && (!h || !mask)) return fail(ctx, DCTAE_EINVAL, "bad LFQ tensors");
+  if (!(temperature != 0.0f)) return fail(ctx, DCTAE_EINVAL, "temperature must not be 0");
+  return 0;
+}
+
+int dctae_lfq_entropy_forward(dctae_ctx* ctx, const dctae_lfq* lfq, const float* h, const uint8_t* mask,
+                              int64_t n_tok, float temperature, float eps, float* avg_probs, float* scalars,
+                              void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  int rc;
+  if ((rc = lfq_entropy_check(ctx, lfq, h, mask, n_tok, temperature))) return rc;
+  if (!avg_probs || !scalars) return fail(ctx, DCTAE_EINVAL, "NULL output");
+  if ((rc = ensure_ws(ctx, sizeof(float) * lfq_entropy_fwd_ws_floats(n_tok, lfq->num_codebooks, lfq->codebook_dim),
+                      256)))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "lfq_entropy_forward");
+  launch_lfq_entropy_fwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature, eps,
+                         ctx->ws, avg_probs, scalars, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_lfq_entropy_backward(dctae_ctx* ctx, const dctae_lfq* lfq, const float* h, const uint8_t* mask,
+                               int64_t n_tok, float temperature, float eps, const float* avg_probs,
+                               const float* scalars, const float* grad, float* dh, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  int rc;
+  if ((rc = lfq_entropy_check(ctx, lfq, h, mask, n_tok, temperature))) return rc;
+  if (!avg_probs || !scalars || !grad || (n_tok > 0 && !dh)) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  if (n_tok == 0) return 0;
+  if ((rc = ensure_ws(ctx, sizeof(float) * lfq_entropy_bwd_ws_floats(lfq->codebook_dim), 256))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "lfq_entropy_backward");
+  if (launch_lfq_entropy_bwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature,
+                             eps, avg_probs, scalars, grad, ctx->ws, dh, s))
+    return fail(ctx, DCTAE_EHIP, "LFQ entropy backward: the kernel's LDS size could not be set");
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_linear_ordered(dctae_ctx* ctx, const float* x, int64_t n, int32_t K, const float* wt, const float* b,
+                         int32_t dim, float* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  if (n < 0 || K < 1 || dim < 1 || n / 16 >= (int64_t)INT32_MAX) return fail(ctx, DCTAE_EINVAL, "bad linear shape");
+  if (!linear_ordered_supported(K, dim)) return fail(ctx, DCTAE_EUNSUP, "ordered linear: K <= 512");
+  if (n == 0) return 0;
+  if (!x || !wt || !out) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "linear_ordered");
+  launch_linear_ordered(x, n, K, wt, b, dim, out, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+static int lfq_proj_check(dctae_ctx* ctx, const dctae_lfq* lfq, int64_t n, int32_t dim, const void* a,
+                          const float* w, const void* o, int max_ncb, bool o_vec = false) {
+  if (!lfq || lfq->codebook_dim < 1 || lfq->codebook_dim > 31 || lfq->num_codebooks < 1 ||
+      lfq->num_codebooks > max_ncb)
+    return fail(ctx, DCTAE_EINVAL, "bad LFQ config (codebook_dim <= 31, num_codebooks <= " + std::to_string(max_ncb) + ")");
+  const int64_t cdims = (int64_t)lfq->codebook_dim * lfq->num_codebooks;
+  if (dim < 4 || dim > 256 || dim % 4 != 0 || cdims > 256 || cdims % 4 != 0)
+    return fail(ctx, DCTAE_EINVAL, "LFQ projections: dim and codebook_dim * num_codebooks must be multiples of 4 <= 256");
+  if (n < 0 || (n > 0 && (!a || !w || !o))) return fail(ctx, DCTAE_EINVAL, "bad LFQ projection tensors");
+  if (((uintptr_t)a | (uintptr_t)w) & 15) return fail(ctx, DCTAE_EINVAL, "LFQ projections need 16-byte aligned tensors");
+  // project_out writes its (n, dim) fp32 rows as 16-byte pieces
+  if (o_vec && ((uintptr_t)o & 15))
+    return fail(ctx, DCTAE_EINVAL, "LFQ project_out needs a 16-byte aligned output tensor");
+  return 0;
+}
+
+static int lfq_project_in_impl(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x, int64_t n, int32_t dim,
+                               const float* w, const float* b, float x_bound, int64_t* idx, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (int rc = lfq_proj_check(ctx, lfq, n, dim, x, w, idx, 64)) return rc;
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = proj_scratch(ctx, lfq->codebook_dim * lfq->num_codebooks, dim)) return rc;
+  // ctx->proj_ws (the pre-split weight) is shared with every call of this
+  // context: ordered after the previous call, whatever its stream
+  order_after_previous(ctx, s);
+  {
+    Timer t(ctx, s, "lfq_project_in");
+    launch_lfq_project_in(x, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, idx,
+                          ctx->proj_ws, s, ctx->opt.gemm_h2 ? x_bound : 0.0f, ctx->opt.lfq_ws != 0);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+int dctae_lfq_project_in(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x, int64_t n, int32_t dim,
+                         const float* w, const float* b, int64_t* idx, void* stream) {
+  return lfq_project_in_impl(ctx, lfq, x, n, dim, w, b, 0.0f, idx, stream);
+}
+
+int dctae_lfq_project_in_bounded(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x, int64_t n, int32_t dim,
+                                 const float* w, const float* b, float x_bound, int64_t* idx, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (!(x_bound > 0.0f) || !std::isfinite(x_bound)) return fail(ctx, DCTAE_EINVAL, "x_bound must be finite and > 0");
+  return lfq_project_in_impl(ctx, lfq, x, n, dim, w, b, x_bound, idx, stream);
+}
+
+int dctae_lfq_project_out(dctae_ctx* ctx, const dctae_lfq* lfq, const int64_t* idx, int64_t n, int32_t dim,
+                          const float* w, const float* b, float* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (int rc = lfq_proj_check(ctx, lfq, n, dim, idx, w, out, 32, true)) return rc;
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = proj_scratch(ctx, dim, lfq->codebook_dim * lfq->num_codebooks)) return rc;
+  order_after_previous(ctx, s);   // shared ctx->proj_ws
+  {
+    Timer t(ctx, s, "lfq_project_out");
+    launch_lfq_project_out(idx, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out,
+                           ctx->proj_ws, s, nullptr, nullptr, nullptr, nullptr, 0.f, 0, 0, nullptr, ctx->opt.gemm_h2 != 0,
+                           ctx->opt.lfq_ws != 0);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+int dctae_lfq_project_out_inverse_norm(dctae_ctx* ctx, const dctae_lfq* lfq, const int64_t* idx, int64_t n,
+                                       int32_t dim, const float* w, const float* b, const dctae_norm* norm,
+                                       int32_t max_patch_h, int32_t max_patch_w, const int64_t* channels,
+                                       const int64_t* positions, float* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (int rc = lfq_proj_check(ctx, lfq, n, dim, idx, w, out, 32, true)) return rc;
+  if (!norm || !norm->median_dev || !norm->b_dev || max_patch_h < 1 || max_patch_w < 1 ||
+      (n > 0 && (!channels || !positions)))
+    return fail(ctx, DCTAE_EINVAL, "inverse PatchNorm needs tables, max_patch_h/w and channels / positions");
+  // the fused inverse reads the (3, max_patch_h, max_patch_w, dim) tables and
+  // writes out as float4 pieces along each token's dim floats
+  if (((uintptr_t)norm->median_dev | (uintptr_t)norm->b_dev | (uintptr_t)out) & 15)
+    return fail(ctx, DCTAE_EINVAL, "fused inverse PatchNorm needs 16-byte aligned median / b / out");
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = proj_scratch(ctx, dim, lfq->codebook_dim * lfq->num_codebooks)) return rc;
+  order_after_previous(ctx, s);   // shared ctx->proj_ws
+  {
+    Timer t(ctx, s, "lfq_project_out");
+    launch_lfq_project_out(idx, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out,
+                           ctx->proj_ws, s, channels, positions, norm->median_dev, norm->b_dev, norm->eps, max_patch_h,
+                           max_patch_w, ctx->err_dev, ctx->opt.gemm_h2 != 0, ctx->opt.lfq_ws != 0);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+// ---- VectorQuantize inference (dctae_vq.hip) --------------------------------
+static int vq_check(dctae_ctx* ctx, const dctae_vq* vq) {
+  if (!vq || vq->codebook_dim != 16 || vq->heads < 1 || vq->codebook_size < 1 || vq->dim < 1 || !vq->embed_dev)
+    return fail(ctx, DCTAE_EINVAL, "bad VectorQuantize config (codebook_dim 16, heads >= 1, codebook_size >= 1)");
+  const bool proj = vq->dim != vq->heads * vq->codebook_dim;   // vector_quantize.py:725-728
+  if (proj && (!vq->w_in_dev || !vq->b_in_dev || !vq->w_out_dev || !vq->b_out_dev))
+    return fail(ctx, DCTAE_EINVAL, "VectorQuantize: dim != heads * codebook_dim needs project_in / project_out");
+  if (vq->affine && (!vq->codebook_mean_dev || !vq->codebook_variance_dev || !vq->batch_mean_dev ||
+                     !vq->batch_variance_dev || !vq->batch_initted_dev))
+    return fail(ctx, DCTAE_EINVAL, "VectorQuantize: affine_param needs codebook / batch statistics");
+  return 0;
+}
+
+static int vq_scratch(dctae_ctx* ctx, size_t need) {
+  if (need <= ctx->vq_bytes) return 0;
+  HIPCHK(ctx, hipDeviceSynchronize());
+  if (ctx->vq_ws) hipFree(ctx->vq_ws);
+  ctx->vq_ws = nullptr;
+  ctx->vq_bytes = 0;
+  if (hipMalloc((void**)&ctx->vq_ws, need) != hipSuccess)
+    return fail(ctx, DCTAE_ENOMEM, "VectorQuantize scratch allocation of " + std::to_string(need) + " bytes failed");
+  ctx->vq_bytes = need;
+  return 0;
+}
+
+// O (n, N) = A (n, K) W^T (N, K) + bias, on k_gemm_f32 (plan uploaded through the shared plan buffer)
+static int vq_linear(dctae_ctx* ctx, const float* A, int64_t n, int K, const float* W, const float* bias, int N,
+                     float* O, const uint8_t* mask, const float* orig, hipStream_t s, const char* name) {
+  // k_gemm_x3 addresses each operand through a buffer resource with a 32-bit
+  // byte range: the rows go in chunks whose A and O spans stay below 2^31 bytes
+  const int64_t rows_max = ((int64_t)1 << 31) / ((int64_t)4 * std::max(K, N)) - 1;
+  std::vector<GemmProblem> g;
+  std::vector<TileRef> t;
+  for (int64_t r0 = 0; r0 < n; r0 += rows_max) {
+    const int rows = (int)std::min(rows_max, n - r0);
+    g.push_back(gemm(A + r0 * K, 0, K, 1, W, 0, K, 1, O + r0 * N, 0, N, 1, rows, N, K, 1));
+    add_tiles(t, (int)g.size() - 1, g.back());
+  }
+  PlanBuf pb;
+  const size_t g_off = pb.add(g.data(), g.size());
+  const size_t t_off = pb.add(t.data(), t.size());
+  int rc;
+  if ((rc = upload_plan(ctx, pb, s))) return rc;
+  Timer tm(ctx, s, name);
+  ctx_gemm(ctx, 1, (const GemmProblem*)(ctx->plan_dev + g_off), (const TileRef*)(ctx->plan_dev + t_off), (int)t.size(), s);
+  launch_vq_bias(O, bias, n, N, mask, orig, s);
+  return 0;
+}
+
+int dctae_vq_forward(dctae_ctx* ctx, const dctae_vq* vq, const float* x, const uint8_t* mask, int64_t n_tok,
+                     float* quantize, int64_t* indices, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  int rc = vq_check(ctx, vq);
+  if (rc) return rc;
+  if (n_tok < 0 || (n_tok > 0 && (!x || !indices))) return fail(ctx, DCTAE_EINVAL, "bad VectorQuantize tensors");
+  if (n_tok == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const int H = vq->heads, D = vq->codebook_dim, C = vq->codebook_size, HD = H * D;
+  // element indices of the (n_tok, dim) input and the (n_tok, H*D) vectors are 32-bit in the kernels
+  if (n_tok > (int64_t)INT32_MAX / 64 || n_tok * std::max(vq->dim, HD) > (int64_t)INT32_MAX)
+    return fail(ctx, DCTAE_EINVAL, "VectorQuantize: too many tokens in one call (n_tok * max(dim, heads * 16) >= 2^31)");
+  const bool proj = vq->dim != HD;
+  const int64_t nv = n_tok * H;
+  // scratch: acc (64 doubles) | et (C*D) | y2 (C) | xp (n*HD, projected only) | xq (n*HD)
+  const size_t acc_b = 64 * sizeof(double);
+  const size_t et_b = ((size_t)C * D * 4 + 255) & ~size_t(255);
+  const size_t y2_b = ((size_t)C * 4 + 255) & ~size_t(255);
+  const size_t v_b = ((size_t)nv * D * 4 + 255) & ~size_t(255);
+  const bool need_xq = quantize != nullptr;
+  if ((rc = vq_scratch(ctx, acc_b + et_b + y2_b + (proj ? v_b : 0) + ((need_xq && (proj || mask)) ? v_b : 0))))
+    return rc;
+  uint8_t* p = ctx->vq_ws;
+  double* acc = (double*)p;
+  float* et = (float*)(p + acc_b);
+  float* y2 = (float*)(p + acc_b + et_b);
+  uint8_t* q = p + acc_b + et_b + y2_b;
+  float* xp = proj ? (float*)q : const_cast<float*>(x);
+  if (proj) q += v_b;
+  // codes: straight into quantize when nothing follows them
+  float* xq = need_xq ? ((proj || mask) ? (float*)q : quantize) : nullptr;
+  order_after_previous(ctx, s);
+  if (proj && (rc = vq_linear(ctx, x, n_tok, vq->dim, vq->w_in_dev, vq->b_in_dev, HD, xp, nullptr, nullptr, s,
+                              "vq_project_in")))
+    return rc;
+  {
+    Timer t(ctx, s, "vq_codebook");
+    if (vq->affine) {
+      HIPCHK(ctx, hipMemsetAsync(acc, 0, acc_b, s));
+      launch_vq_stats(xp, mask, n_tok, H, acc, s);
+    }
+    launch_vq_codebook(acc, vq->batch_mean_dev, vq->batch_variance_dev, vq->batch_initted_dev, vq->affine_decay,
+                       vq->affine, vq->embed_dev, vq->codebook_mean_dev, vq->codebook_variance_dev, C, et, y2, s);
+  }
+  {
+    Timer t(ctx, s, "vq_assign");
+    launch_vq_assign(xp, nv, H, et, y2, C, xq, indices, s);
+  }
+  if (need_xq) {
+    if (proj) {
+      if ((rc = vq_linear(ctx, xq, n_tok, HD, vq->w_out_dev, vq->b_out_dev, vq->dim, quantize, mask, x, s,
+                          "vq_project_out")))
+        return rc;
+    } else if (mask) {
+      HIPCHK(ctx, hipMemcpyAsync(quantize, xq, sizeof(float) * nv * D, hipMemcpyDeviceToDevice, s));
+      launch_vq_bias(quantize, nullptr, n_tok, HD, mask, x, s);
+    }
+  }
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+int dctae_vq_codes_from_indices(dctae_ctx* ctx, const dctae_vq* vq, const int64_t* idx, int64_t n, float* codes,
+                                void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  int rc = vq_check(ctx, vq);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!idx || !codes))) return fail(ctx, DCTAE_EINVAL, "bad VectorQuantize tensors");
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "vq_codes");
+  launch_vq_codes(idx, n * vq->heads, vq->embed_dev, vq->codebook_size, codes, ctx->err_dev, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_vq_output_from_indices(dctae_ctx* ctx, const dctae_vq* vq, const int64_t* idx, int64_t n, float* out,
+                                 void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  int rc = vq_check(ctx, vq);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!idx || !out))) return fail(ctx, DCTAE_EINVAL, "bad VectorQuantize tensors");
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const int HD = vq->heads * vq->codebook_dim;
+  if (vq->dim == HD) return dctae_vq_codes_from_indices(ctx, vq, idx, n, out, stream);
+  if ((rc = vq_scratch(ctx, ((size_t)n * HD * 4 + 255) & ~size_t(255)))) return rc;
+  float* codes = (float*)ctx->vq_ws;
+  order_after_previous(ctx, s);
+  {
+    Timer t(ctx, s, "vq_codes");
+    launch_vq_codes(idx, n * vq->heads, vq->embed_dev, vq->codebook_size, codes, ctx->err_dev, s);
+  }
+  if ((rc = vq_linear(ctx, codes, n, HD, vq->w_out_dev, vq->b_out_dev, vq->dim, out, nullptr, nullptr, s,
+                      "vq_project_out")))
+    return rc;
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// DCTAutoencoder transformer operators (dctae_model.hip)
+// ---------------------------------------------------------------------------
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int dctae_model_linear(dctae_ctx* ctx, int64_t M, int32_t N, int32_t K, const uint16_t* x, int64_t ldx,
+                       const uint16_t* w, int32_t w_rows, int64_t ldw, const float* bias, int32_t epilogue, void* out,
+                       int64_t ldo, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || N <= 0 || K <= 0 || K % 64 || w_rows < N || ldx < K || ldw < K || ldx % 8 || ldw % 8 || ldo < N)
+    return fail(ctx, DCTAE_EINVAL, "model_linear: bad shape (K % 64, ld % 8, w_rows >= N, ld >= K / N)");
+  if (epilogue < DCTAE_LIN_F32 || epilogue > DCTAE_LIN_F32_RESIDUAL) return fail(ctx, DCTAE_EINVAL, "model_linear: epilogue");
+  if (M == 0) return 0;
+  if (!x || !w || !out || !al16(x) || !al16(w)) return fail(ctx, DCTAE_EINVAL, "model_linear: null or unaligned tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  LinearArgs a{x, w, bias, out, M, ldx, ldw, ldo, N, w_rows, K};
+  Timer t(ctx, s, "model_linear");
+  launch_linear(a, epilogue, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_attention(dctae_ctx* ctx, int32_t R, int32_t S, int32_t heads, int32_t head_dim, const uint16_t* qkv,
+                          const int64_t* ids, const uint8_t* key_pad, uint16_t* out, int64_t ldo, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (head_dim != 64) return fail(ctx, DCTAE_EUNSUP, "model_attention: head_dim must be 64");
+  if (R < 0 || S <= 0 || heads <= 0 || ldo < 64ll * heads || ldo % 8)
+    return fail(ctx, DCTAE_EINVAL, "model_attention: bad shape");
+  if (R == 0) return 0;
+  if (!qkv || !ids || !key_pad || !out || !al16(qkv) || !al16(out))
+    return fail(ctx, DCTAE_EINVAL, "model_attention: null or unaligned tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  AttnArgs a{qkv, ids, key_pad, out, R, S, heads, (int32_t)ldo, 0.125f};
+  Timer t(ctx, s, "model_attention");
+  launch_attention(a, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+static int ln_check(dctae_ctx* ctx, int64_t M, int32_t D, const float* x, const float* g, const float* b) {
+  if (M < 0 || D <= 0 || D > 4096) return fail(ctx, DCTAE_EINVAL, "model layernorm: bad shape (D <= 4096)");
+  if (M > 0 && (!x || !g || !b)) return fail(ctx, DCTAE_EINVAL, "model layernorm: null tensor");
+  return 0;
+}
+
+int dctae_model_layernorm(dctae_ctx* ctx, int64_t M, int32_t D, const float* x, int64_t ldx, const float* g,
+                          const float* b, float eps, uint16_t* out, int64_t ldo, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  int rc = ln_check(ctx, M, D, x, g, b);
+  if (rc || M == 0) return rc;
+  if (!out) return fail(ctx, DCTAE_EINVAL, "model_layernorm: null output");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  LnArgs a{};
+  a.x = x; a.gamma = g; a.beta = b; a.out_bf16 = out; a.M = M; a.ldx = ldx; a.ldo = ldo; a.D = D; a.eps = eps;
+  Timer t(ctx, s, "model_layernorm");
+  launch_layernorm(a, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_embed_norm(dctae_ctx* ctx, int64_t M, int32_t D, const float* x, int64_t ldx, const float* g,
+                           const float* b, float eps, const float* ph, const float* pw, const float* pc,
+                           const int64_t* ch, const int64_t* pos, float* out, int64_t ldo, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  int rc = ln_check(ctx, M, D, x, g, b);
+  if (rc || M == 0) return rc;
+  if (!out || !ph || !pw || !pc || !ch || !pos) return fail(ctx, DCTAE_EINVAL, "model_embed_norm: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  LnArgs a{};
+  a.x = x; a.gamma = g; a.beta = b; a.out_f32 = out; a.pos_h = ph; a.pos_w = pw; a.pos_c = pc; a.ch = ch;
+  a.pos = pos; a.M = M; a.ldx = ldx; a.ldo = ldo; a.D = D; a.eps = eps;
+  Timer t(ctx, s, "model_embed_norm");
+  launch_layernorm(a, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_pos_add(dctae_ctx* ctx, int64_t M, int32_t D, float* x, int64_t ldx, const float* ph, const float* pw,
+                        const float* pc, const int64_t* ch, const int64_t* pos, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || D <= 0) return fail(ctx, DCTAE_EINVAL, "model_pos_add: bad shape");
+  if (M == 0) return 0;
+  if (!x || !ph || !pw || !pc || !ch || !pos) return fail(ctx, DCTAE_EINVAL, "model_pos_add: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  PosArgs a{x, ph, pw, pc, ch, pos, M, ldx, D};
+  Timer t(ctx, s, "model_pos_add");
+  launch_pos_add(a, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_to_bf16(dctae_ctx* ctx, int64_t M, int32_t K, const float* x, int64_t ldx, int32_t Kp, uint16_t* out,
+                        void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || K < 0 || Kp < K || ldx < K) return fail(ctx, DCTAE_EINVAL, "model_to_bf16: bad shape");
+  if (M == 0 || Kp == 0) return 0;
+  if (!x || !out) return fail(ctx, DCTAE_EINVAL, "model_to_bf16: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "model_to_bf16");
+  launch_to_bf16(x, ldx, M, K, Kp, out, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_lfq(dctae_ctx* ctx, int64_t M, int32_t ncb, int32_t cbd, float scale, const float* x, int64_t ldx,
+                    int64_t* codes, uint16_t* q_bf16, float* q_f32, int64_t ldq, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || ncb <= 0 || cbd <= 0 || cbd > 62 || ldx < (int64_t)ncb * cbd || ((q_bf16 || q_f32) && ldq < (int64_t)ncb * cbd))
+    return fail(ctx, DCTAE_EINVAL, "model_lfq: bad shape");
+  if (M == 0) return 0;
+  if (!x || !codes) return fail(ctx, DCTAE_EINVAL, "model_lfq: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  LfqArgs a{x, codes, q_bf16, q_f32, M, ldx, ldq, ncb, cbd, scale};
+  Timer t(ctx, s, "model_lfq");
+  launch_lfq_codes(a, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

@@ -25,7 +25,7 @@
 //         load; output T[c][y][kx], kx < Kw (the layout the column kernels read)
 //   cols: job = (column pair) of one channel of T; output Y[c][ky][kx], ky < Kh,
 //         then k_tile_epilogue as on the GEMM path.
-// Tables (host, float64 -> fp32; dctae_api.hip): W_L^m (m < L), c[n], e_k
+// Tables (host, float64 -> fp32; dctae_plan.hip): W_L^m (m < L), c[n], e_k
 // (n, k < N), Bhat (L).
 #include "dctae_device.h"
 #include "dctae_fft_common.h"

@@ -1,0 +1,201 @@
+// The context behind the C ABI and what its host units share: error
+// reporting, per-launch timing, plan upload, workspace, and the planning
+// helpers of dctae_plan.hip.  Host code only (no kernels).
+//   dctae_api.hip      context, options, timing, plan upload, workspace
+//   dctae_plan.hip     DCT matrices, GEMM problems and tile lists, FFT / Bluestein plans
+//   dctae_encode.hip   the encode plan and launch sequence
+//   dctae_decode.hip   the decode launch sequences
+//   dctae_api_ops.hip  PatchNorm, LFQ, VectorQuantize and transformer entry points
+#pragma once
+#include <cmath>
+#include <complex>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/dctae.h"
+#include "dctae_internal.h"
+#include "dctae_launch.h"
+#include "dctae_options.h"
+
+struct TimedLaunch {
+  const char* name;
+  hipEvent_t a, b;
+};
+
+struct TimingEntry {
+  std::string name;
+  double ms = 0.0;
+  int64_t launches = 0;
+};
+
+struct dctae_ctx {
+  int device = 0;
+  std::string err;
+  dctae::Options opt;   // the dctae_set_option switches (dctae_options.h)
+  // DCT-II matrices C_N[rows][N] (fp32, from float64), keyed by (N, rows)
+  std::map<std::pair<int, int>, float*> dct;
+  // the same matrices pre-split for k_gemm_x3 (GemmProblem::Xs), by fp32 pointer
+  struct X3Mat {
+    uint16_t* d;
+    int R, K, Rp, Kp;
+    uint16_t* dh;   // k_gemm_h2: two fp16 planes [2][Rp][Kp] of the matrix scaled by 2^hexp
+    int hexp;
+  };
+  std::map<const float*, X3Mat> dct_x3;
+  // workspace (floats) and token staging (bytes), grow-only
+  float* ws = nullptr;
+  size_t ws_bytes = 0;
+  uint8_t* stage = nullptr;
+  size_t stage_bytes = 0;
+  // plan: host (pinned) + device copies, last uploaded plan bytes for caching
+  uint8_t* plan_host = nullptr;
+  uint8_t* plan_dev = nullptr;
+  size_t plan_cap = 0;
+  std::vector<uint8_t> plan_last;
+  uint64_t plan_last_id = 0, plan_counter = 0;
+  hipEvent_t plan_evt = nullptr;
+  hipEvent_t done_evt = nullptr;
+  // the encode's side stream (SideStream in dctae_encode.hip; created on first use)
+  hipStream_t side = nullptr;
+  hipEvent_t side_in = nullptr, side_out = nullptr;
+  hipStream_t last_stream = nullptr;
+  bool have_done = false;
+  int* err_dev = nullptr;
+  dctae::ColorMats cm{};
+  // FFT-DCT plans: tables (W_M^k, alpha/beta) in one device buffer
+  float2* fft_tab = nullptr;
+  int64_t fft_tab_cap = 0, fft_tab_used = 0;
+  std::map<int, dctae::FftPlan> fft_plans;   // N -> plan (N = 0 entries never stored)
+  std::map<int, dctae::FftPlan> bs_plans;    // N -> Bluestein plan (kind 1; kind 0 = none)
+  std::map<int, int64_t> bs_tw;              // L -> offset of W_L^m in fft_tab
+  size_t lds_limit = 64 * 1024;              // dynamic LDS the FFT kernels may use
+  int n_cu = 256;
+  // PatchNorm training scratch (token cell ids, per-cell lists, batch tables), grow-only
+  uint8_t* st_ws = nullptr;
+  size_t st_bytes = 0;
+  // VectorQuantize scratch (projected vectors, codes, transformed codebook), grow-only
+  uint8_t* vq_ws = nullptr;
+  size_t vq_bytes = 0;
+  // LFQ projection scratch (the pre-split weight planes), grow-only
+  uint16_t* proj_ws = nullptr;
+  size_t proj_bytes = 0;
+  // cached encode plan: valid for enc_key (the call's inputs and the
+  // plan-shaping options) while the workspace stays at enc_ws
+  std::vector<int64_t> enc_key;
+  const float* enc_ws = nullptr;
+  struct EncPlan* enc_plan = nullptr;
+  // timing
+  bool timing = false;
+  std::vector<TimedLaunch> pending;
+  std::vector<hipEvent_t> evt_pool;
+  std::vector<TimingEntry> totals;
+};
+
+namespace dctae {
+
+// the last error of a call that had no context to keep it (dctae_last_error(NULL))
+extern thread_local std::string g_err;
+
+inline int fail(dctae_ctx* ctx, int code, const std::string& msg) {
+  if (ctx) ctx->err = msg;
+  g_err = msg;
+  return code;
+}
+
+#define HIPCHK(ctx, expr)                                                              \
+  do {                                                                                 \
+    hipError_t _e = (expr);                                                            \
+    if (_e != hipSuccess)                                                              \
+      return fail(ctx, DCTAE_EHIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
+  } while (0)
+
+struct Timer {
+  dctae_ctx* ctx;
+  hipStream_t s;
+  const char* name;
+  hipEvent_t a = nullptr;
+  Timer(dctae_ctx* c, hipStream_t st, const char* n) : ctx(c), s(st), name(n) {
+    if (ctx->timing) {
+      a = take();
+      hipEventRecord(a, s);
+    }
+  }
+  hipEvent_t take() {
+    if (ctx->evt_pool.empty()) {
+      hipEvent_t e;
+      hipEventCreate(&e);
+      return e;
+    }
+    hipEvent_t e = ctx->evt_pool.back();
+    ctx->evt_pool.pop_back();
+    return e;
+  }
+  ~Timer() {
+    if (ctx->timing) {
+      hipEvent_t b = take();
+      hipEventRecord(b, s);
+      ctx->pending.push_back({name, a, b});
+    }
+  }
+};
+
+// ---- plan serialisation ----------------------------------------------------
+struct PlanBuf {
+  std::vector<uint8_t> bytes;
+  template <class T>
+  size_t add(const T* p, size_t n) {
+    size_t off = (bytes.size() + 255) & ~size_t(255);
+    bytes.resize(off + n * sizeof(T));
+    if (n) std::memcpy(bytes.data() + off, p, n * sizeof(T));
+    return off;
+  }
+};
+
+// order this call after the previous one on a possibly different stream
+inline void order_after_previous(dctae_ctx* ctx, hipStream_t s) {
+  if (ctx->have_done && ctx->last_stream != s) hipStreamWaitEvent(s, ctx->done_evt, 0);
+}
+
+inline void mark_done(dctae_ctx* ctx, hipStream_t s) {
+  hipEventRecord(ctx->done_evt, s);
+  ctx->last_stream = s;
+  ctx->have_done = true;
+}
+
+inline void ctx_gemm(const dctae_ctx* ctx, int nc, const GemmProblem* probs, const TileRef* tiles, int n_tiles,
+                     hipStream_t s, int share = 0) {
+  if (ctx->opt.gemm_x3)
+    launch_gemm_x3(nc, probs, tiles, n_tiles, s, share);
+  else
+    launch_gemm(nc, probs, tiles, n_tiles, s, share);
+}
+
+// ---- dctae_api.hip ----
+int upload_plan(dctae_ctx* ctx, const PlanBuf& pb, hipStream_t s, uint64_t plan_id = 0);
+int ensure_ws(dctae_ctx* ctx, size_t ws_bytes, size_t stage_bytes);
+
+// ---- dctae_plan.hip ----
+int dct_matrix(dctae_ctx* ctx, int N, int rows, const float** out, int parity = -1);
+int proj_scratch(dctae_ctx* ctx, int N, int K);
+void attach_x3(const dctae_ctx* ctx, GemmProblem& g);
+int check_cfg(dctae_ctx* ctx, const dctae_fe_cfg* cfg);
+int check_lfq(dctae_ctx* ctx, const dctae_lfq* lfq, int PP);
+int describe(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int H, int W, ImgDesc& d);
+GemmProblem gemm(const float* A, int64_t sAc, int64_t sAm, int64_t sAk, const float* B, int64_t sBc, int64_t sBn,
+                 int64_t sBk, float* O, int64_t sOc, int64_t sOm, int64_t sOn, int M, int N, int K, int C);
+void xcd_deal_tiles(std::vector<TileRef>& t, const GemmProblem* probs, int share);
+void add_tiles(std::vector<TileRef>& t, int prob, const GemmProblem& g);
+EncParams enc_params(const dctae_fe_cfg* cfg, const dctae_norm* norm, const dctae_lfq* lfq);
+int next_pow2(int x);
+int bs_plan_for(dctae_ctx* ctx, int N, FftPlan* out);
+int fft_plan_for(dctae_ctx* ctx, int N, int P, FftPlan* out);
+// the Bluestein block lists of a chunk job are kept per FFT length L
+inline int bs_lidx(int L) { return L == 256 ? 0 : L == 512 ? 1 : L == 1024 ? 2 : 3; }
+constexpr int kBsL[4] = {256, 512, 1024, 2048};
+
+// ---- dctae_encode.hip ----
+void drop_encode_plan(dctae_ctx* ctx);   // dctae_ctx_destroy: EncPlan is complete only there
+
+}  // namespace dctae

@@ -1,0 +1,274 @@
+// The decode engine: dctae_decode and dctae_decode_normed.
+#include "dctae_ctx.h"
+
+using namespace dctae;
+
+// the token-side arguments of the decode kernels; normed: `patches` are
+// PatchNorm outputs that the kernel inverts (the FFT path's column kernel)
+static DecodeArgs decode_args(const dctae_ctx* ctx, const dctae_fe_cfg* cfg, const int64_t* ids,
+                              const uint8_t* key_pad, const int64_t* pos, const int64_t* ch, const dctae_norm* norm,
+                              const dctae_lfq* lfq, const int64_t* codes, const float* patches, const int32_t* lut,
+                              int32_t lut_w, bool normed) {
+  DecodeArgs a{};
+  a.ids = ids;
+  a.key_pad = key_pad;
+  a.pos = pos;
+  a.ch = ch;
+  a.codes = codes;
+  a.patches = patches;
+  a.lut = lut;
+  a.lut_w = lut_w;
+  a.S = cfg->max_seq_len;
+  a.P = cfg->patch_size;
+  a.use_codes = codes ? 1 : (normed ? 2 : 0);
+  if (codes) {
+    a.cb_dim = lfq->codebook_dim;
+    a.ncb = lfq->num_codebooks;
+    a.scale = lfq->codebook_scale;
+  }
+  if (codes || normed) {
+    a.median = norm->median_dev;
+    a.b = norm->b_dev;
+    a.eps = norm->eps;
+  }
+  a.maxph = cfg->max_patch_h;
+  a.maxpw = cfg->max_patch_w;
+  a.err = ctx->err_dev;
+  return a;
+}
+
+// decode of 512 x 512 images on the FFT path: token map -> column DCT-III
+// (tokens expanded in the kernel) -> U -> row DCT-III + IPT -> RGB
+static int decode_fft(dctae_ctx* ctx, const dctae_fe_cfg* cfg, std::vector<ImgDesc>& D, const FftPlan& fpl,
+                      int32_t n_rows, const int32_t* img_lut, int32_t lut_w, const int64_t* ids,
+                      const uint8_t* key_pad, const int64_t* pos, const int64_t* ch, const dctae_norm* norm,
+                      const dctae_lfq* lfq, const int64_t* codes, const float* patches, float* rgb, hipStream_t s,
+                      bool normed) {
+  const int n_img = (int)D.size();
+  const int S = cfg->max_seq_len;
+  int64_t wsf = 0;
+  std::vector<int2> rb;
+  for (int i = 0; i < n_img; ++i) {
+    ImgDesc& d = D[i];
+    d.ws_t = wsf;
+    wsf += (3ll * d.H * d.Kw + 63) & ~63ll;
+    for (int y0 = 0; y0 < d.H; y0 += 16) rb.push_back(make_int2(i, y0));
+  }
+  const int64_t map_off = wsf;
+  const int64_t map_n = (int64_t)n_img * 3 * cfg->max_patch_h * cfg->max_patch_w;
+  wsf += map_n;
+  int rc;
+  if ((rc = ensure_ws(ctx, (size_t)wsf * 4, 256))) return rc;
+  PlanBuf pb;
+  const size_t d_off = pb.add(D.data(), D.size());
+  const size_t rb_off = pb.add(rb.data(), rb.size());
+  const size_t lut_off = pb.add(img_lut, (size_t)n_rows * lut_w);
+  order_after_previous(ctx, s);
+  if ((rc = upload_plan(ctx, pb, s))) return rc;
+  uint8_t* pd = ctx->plan_dev;
+  const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
+  int32_t* map = (int32_t*)(ctx->ws + map_off);
+  HIPCHK(ctx, hipMemsetAsync(map, 0xFF, (size_t)map_n * 4, s));
+  const DecodeArgs a = decode_args(ctx, cfg, ids, key_pad, pos, ch, norm, lfq, codes, patches,
+                                   (const int32_t*)(pd + lut_off), lut_w, normed);
+  const float2* tw = ctx->fft_tab + fpl.tw_off;
+  const float4* pre = reinterpret_cast<const float4*>(ctx->fft_tab + fpl.ipre_off);
+  {
+    Timer t(ctx, s, "dec_map");
+    launch_dec_map((int64_t)n_rows * S, dd, a, map, s);
+  }
+  // 32 kept tile columns on the default row kernel: U in the band layout
+  // (k_idct_cols512b); otherwise row-major U (k_idct_cols512)
+  const bool rows512 = ctx->opt.dec_rows_kernel == 3 && D[0].qw == 32;
+  const bool band = rows512 && ctx->opt.dec_cols_kernel == 2;
+  {
+    Timer t(ctx, s, "idct_cols");
+    if (band)
+      launch_idct_cols512b(dd, n_img, ctx->ws, map, tw, pre, a, s);
+    else
+      launch_idct_cols512(dd, n_img, D[0].qw, ctx->ws, map, tw, pre, a, s);
+  }
+  {
+    Timer t(ctx, s, "idct_rows");
+    if (rows512)
+      launch_idct_rows512(band, dd, (const int2*)(pd + rb_off), (int)rb.size(), ctx->ws, rgb, tw, pre, ctx->cm, s);
+    else
+      launch_idct_rows_spec(1, dd, (const int2*)(pd + rb_off), (int)rb.size(), ctx->ws, rgb, tw, pre, ctx->cm, s);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+// normed: patches are PatchNorm outputs (before inverse_norm); the FFT path
+// applies the inverse in its column kernel (the (c, strip) tables of a block
+// are image-independent), other geometries run dctae_norm_inverse's kernel
+// into the staging buffer first
+static int decode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut,
+                       int32_t lut_w, int32_t n_img, const int32_t* out_hw, const int64_t* out_off,
+                       const int32_t* patch_hw, const int64_t* ids, const uint8_t* key_pad, const int64_t* pos,
+                       const int64_t* ch, const dctae_norm* norm, const dctae_lfq* lfq, const int64_t* codes,
+                       const float* patches, float* rgb, void* stream, bool normed) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  int rc = check_cfg(ctx, cfg);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int P = cfg->patch_size, PP = P * P, S = cfg->max_seq_len;
+  if (normed && (!norm || !norm->median_dev || !norm->b_dev || codes))
+    return fail(ctx, DCTAE_EINVAL, "decode of PatchNorm-space patches needs the PatchNorm tables (and no codes)");
+  if (n_rows < 0 || n_img < 0 || lut_w < 1 || !img_lut || (n_img > 0 && (!out_hw || !out_off || !patch_hw || !rgb)))
+    return fail(ctx, DCTAE_EINVAL, "bad decode descriptor");
+  if (n_rows > 0 && (!ids || !key_pad || !pos || !ch)) return fail(ctx, DCTAE_EINVAL, "NULL batch tensor");
+  if (codes) {
+    if (!norm || !norm->median_dev || !norm->b_dev) return fail(ctx, DCTAE_EINVAL, "decode from codes needs PatchNorm");
+    if ((rc = check_lfq(ctx, lfq, PP))) return rc;
+  } else if (n_rows > 0 && !patches) {
+    return fail(ctx, DCTAE_EINVAL, "decode needs codes or patches");
+  }
+  if (n_img == 0) return 0;
+  for (int64_t i = 0; i < (int64_t)n_rows * lut_w; ++i)
+    if (img_lut[i] < -1 || img_lut[i] >= n_img) return fail(ctx, DCTAE_EINVAL, "image LUT entry out of range");
+  std::vector<ImgDesc> D(n_img);
+  int64_t wsf = 0, max_hw = 1;
+  for (int i = 0; i < n_img; ++i) {
+    ImgDesc& d = D[i];
+    std::memset(&d, 0, sizeof(d));
+    d.plan_w = d.plan_h = -1;
+    d.H = out_hw[2 * i];
+    d.W = out_hw[2 * i + 1];
+    d.ph = patch_hw[2 * i];
+    d.pw = patch_hw[2 * i + 1];
+    if (d.ph < 1 || d.pw < 1 || P * d.ph > d.H || P * d.pw > d.W)
+      return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": patch_sizes do not fit original_sizes (FE:304)");
+    d.qh = std::min(d.ph, cfg->max_patch_h);
+    d.qw = std::min(d.pw, cfg->max_patch_w);
+    d.Kh = P * d.qh;
+    d.Kw = P * d.qw;
+    d.rgb_off = out_off[i];
+    d.ws_y = wsf;
+    wsf += 3ll * d.Kh * d.Kw;
+    d.ws_t = wsf;
+    wsf += 3ll * d.H * d.Kw;
+    d.ws_p = wsf;
+    wsf += 3ll * d.H * d.W;
+    max_hw = std::max<int64_t>(max_hw, (int64_t)d.H * d.W);
+  }
+  // the GEMM path's slot map (k_dec_map: the later packed slot wins at a duplicate place, FE:639-643)
+  const int64_t gmap_off = (wsf + 63) & ~63ll;
+  const int64_t gmap_n = (int64_t)n_img * 3 * cfg->max_patch_h * cfg->max_patch_w;
+  // FFT path (dctae_idct.hip): every image 512 x 512 on the specialised plan, recommended LFQ
+  bool fftdec = ctx->opt.fft_decode && P == 14 && (!codes || (lfq->codebook_dim == 14 && lfq->num_codebooks == 14));
+  for (int i = 0; fftdec && i < n_img; ++i)
+    fftdec = D[i].H == 512 && D[i].W == 512 && D[i].qh <= 32 && D[i].qw == D[0].qw;
+  FftPlan fpl{};
+  if (fftdec) fftdec = fft_plan_for(ctx, 512, P, &fpl) == 0 && fpl.spec == 1;
+  if (fftdec)
+    return decode_fft(ctx, cfg, D, fpl, n_rows, img_lut, lut_w, ids, key_pad, pos, ch, norm, lfq, codes, patches,
+                      rgb, s, normed);
+  if (normed && n_rows > 0) {
+    // other geometries: the inverse over every packed token into the staging
+    // buffer (after the previous call, which may still read it), then as patches
+    const int64_t n_tok = (int64_t)n_rows * S;
+    if ((rc = ensure_ws(ctx, 0, (size_t)n_tok * PP * 4))) return rc;
+    order_after_previous(ctx, s);
+    float* inv = reinterpret_cast<float*>(ctx->stage);
+    {
+      Timer t(ctx, s, "norm_inverse");
+      launch_norm(patches, ch, pos, n_tok, PP, cfg->max_patch_h, cfg->max_patch_w, norm->median_dev, norm->b_dev,
+                  norm->eps, norm->min_val, norm->max_val, 1, inv, ctx->err_dev, s);
+    }
+    patches = inv;
+  }
+  if ((rc = ensure_ws(ctx, (size_t)(gmap_off + gmap_n) * 4, 256))) return rc;
+  const int rows_cap = P * std::max(cfg->max_patch_h, cfg->max_patch_w);
+  std::vector<GemmProblem> probs;
+  std::vector<TileRef> t1, t2;
+  for (int i = 0; i < n_img; ++i) {
+    const ImgDesc& d = D[i];
+    const float *CW, *CH;
+    if ((rc = dct_matrix(ctx, d.W, std::min(d.W, rows_cap), &CW))) return rc;
+    if ((rc = dct_matrix(ctx, d.H, std::min(d.H, rows_cap), &CH))) return rc;
+    float* ws = ctx->ws;
+    // U[c][y][kx] = sum_ky CH[ky][y] * Ysp[c][ky][kx]
+    GemmProblem g1 = gemm(CH, 0, 1, d.H, ws + d.ws_y, (int64_t)d.Kh * d.Kw, 1, d.Kw, ws + d.ws_t,
+                          (int64_t)d.H * d.Kw, d.Kw, 1, d.H, d.Kw, d.Kh, 3);
+    // X[c][y][x] = sum_kx U[c][y][kx] * CW[kx][x]
+    GemmProblem g2 = gemm(ws + d.ws_t, (int64_t)d.H * d.Kw, d.Kw, 1, CW, 0, 1, d.W, ws + d.ws_p,
+                          (int64_t)d.H * d.W, d.W, 1, d.H, d.W, d.Kw, 3);
+    attach_x3(ctx, g1);
+    attach_x3(ctx, g2);
+    int pr = (int)probs.size();
+    probs.push_back(g1);
+    probs.push_back(g2);
+    add_tiles(t1, pr, g1);
+    add_tiles(t2, pr + 1, g2);
+  }
+  if (ctx->opt.xcd_order) {   // as the encode's GEMMs (xcd_deal_tiles): speed only
+    xcd_deal_tiles(t1, probs.data(), 2);
+    xcd_deal_tiles(t2, probs.data(), 1);
+  }
+  PlanBuf pb;
+  size_t d_off = pb.add(D.data(), D.size());
+  size_t g_off = pb.add(probs.data(), probs.size());
+  size_t t1_off = pb.add(t1.data(), t1.size());
+  size_t t2_off = pb.add(t2.data(), t2.size());
+  size_t lut_off = pb.add(img_lut, (size_t)n_rows * lut_w);
+  order_after_previous(ctx, s);
+  if ((rc = upload_plan(ctx, pb, s))) return rc;
+  uint8_t* pd = ctx->plan_dev;
+  const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
+  HIPCHK(ctx, hipMemsetAsync(ctx->ws, 0, (size_t)wsf * 4, s));
+  // PatchNorm-space patches were inverted into the staging buffer above: plain patches here
+  const DecodeArgs a = decode_args(ctx, cfg, ids, key_pad, pos, ch, norm, lfq, codes, patches,
+                                   (const int32_t*)(pd + lut_off), lut_w, false);
+  int32_t* gmap = (int32_t*)(ctx->ws + gmap_off);
+  HIPCHK(ctx, hipMemsetAsync(gmap, 0xFF, (size_t)gmap_n * 4, s));
+  {
+    Timer t(ctx, s, "dec_map");
+    launch_dec_map((int64_t)n_rows * S, dd, a, gmap, s);
+  }
+  {
+    Timer t(ctx, s, "scatter_tokens");
+    launch_scatter_tokens((int64_t)n_rows * S, dd, ctx->ws, a, gmap, s);
+  }
+  {
+    Timer t(ctx, s, "idct_cols");
+    ctx_gemm(ctx, 3, (const GemmProblem*)(pd + g_off), (const TileRef*)(pd + t1_off), (int)t1.size(), s, 2);
+  }
+  {
+    Timer t(ctx, s, "idct_rows");
+    ctx_gemm(ctx, 3, (const GemmProblem*)(pd + g_off), (const TileRef*)(pd + t2_off), (int)t2.size(), s, 1);
+  }
+  {
+    Timer t(ctx, s, "ipt_to_rgb");
+    launch_ipt_to_rgb(dd, n_img, max_hw, ctx->ws, rgb, ctx->cm, s);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+extern "C" {
+
+int dctae_decode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut, int32_t lut_w,
+                 int32_t n_img, const int32_t* out_hw, const int64_t* out_off, const int32_t* patch_hw,
+                 const int64_t* ids, const uint8_t* key_pad, const int64_t* pos, const int64_t* ch,
+                 const dctae_norm* norm, const dctae_lfq* lfq, const int64_t* codes, const float* patches,
+                 float* rgb, void* stream) {
+  return decode_impl(ctx, cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch, norm,
+                     lfq, codes, patches, rgb, stream, false);
+}
+
+int dctae_decode_normed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut,
+                        int32_t lut_w, int32_t n_img, const int32_t* out_hw, const int64_t* out_off,
+                        const int32_t* patch_hw, const int64_t* ids, const uint8_t* key_pad, const int64_t* pos,
+                        const int64_t* ch, const dctae_norm* norm, const float* normed_patches, float* rgb,
+                        void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (n_rows > 0 && !normed_patches) return fail(ctx, DCTAE_EINVAL, "decode needs the PatchNorm-space patches");
+  return decode_impl(ctx, cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch, norm,
+                     nullptr, nullptr, normed_patches, rgb, stream, true);
+}
+
+}  // extern "C"

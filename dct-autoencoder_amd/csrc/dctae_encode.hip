@@ -1,0 +1,1057 @@
+// The encode engine: plan, plan cache and launch sequence of dctae_encode,
+// dctae_spectrum_tokens, dctae_dct2 and dctae_patch_spectrum.
+#include "dctae_ctx.h"
+
+using namespace dctae;
+
+// Encode plan: everything the launch sequence needs, cached on the inputs.
+constexpr int kVariants = 3;  // 0 = generic FFT kernels, 1.. = dctae_fft2.hip specialisations
+
+struct ChunkJob {
+  int i0, i1;
+  size_t desc_off, gp_off, rows_t_off, cols_t_off;
+  size_t fr_off[kVariants], fc_off[kVariants];
+  int n_fr[kVariants], n_fc[kVariants];
+  int64_t tw_off[kVariants], post_off_r[kVariants], tw_off_c[kVariants], post_off_c[kVariants];
+  int n_rows_tiles, n_cols_tiles;
+  size_t pc_off;      // k_fft_cols7 list: the spec-1 images of the job (one tile-column count qw)
+  int n_pc, pc_qw;
+  size_t pb_off;      // k_cols512b list: the band-layout images of the job
+  int n_pb;
+  int max_T, any_gemm_rows, any_gemm_cols, fold_t, any_bs_cols;
+  size_t ipt_off;            // k_rgb_to_ipt blocks (local image, first group)
+  int n_ipt;
+  size_t fold_off;           // local indices of the images whose T k_fold_t folds
+  int n_fold;
+  int64_t fold_max_hw;
+  size_t br_off[4], bc_off[4];   // Bluestein row / column blocks per L = 256 .. 2048
+  int n_br[4], n_bc[4];
+  int64_t max_hw;
+  size_t lds_rows, lds_cols;
+  int64_t amax_off;   // k_gemm_h2: |max| bits per image (IPT, T) in the workspace, floats
+  int h2;             // the job's GEMMs on k_gemm_h2
+  size_t epi_off;     // k_tile_epilogue_p blocks (local image, 3 h + c) of the images with Y in the workspace
+  int n_epi;
+  size_t fused_t_off;  // k_rows_fused tiles (row problem, row-pair block)
+  int n_fused_tiles, any_fused;
+};
+
+struct EncPlan {
+  uint64_t id = 0;
+  PlanBuf pb;
+  std::vector<ChunkJob> jobs;
+  size_t all_desc_off = 0;   // every image, global token offsets (sort_pack)
+  int n_img = 0, max_T = 1;
+  int64_t n_tok = 0;
+  size_t rowlen_off = 0, plans_off = 0;
+  size_t ws_need = 0, st_need = 0;
+  int ncb = 0;
+  bool any_pad = true;   // some packed row shorter than max_seq_len
+  bool uniform = false;  // every image of the call has the same (H, W)
+};
+
+// The encode engine.  Full mode (pack != NULL): packed DCTPatches outputs.
+// Token mode (pack == NULL): spectrum tokens in flat order (tokens_dev /
+// scores_dev at tok_off).  Per image the row DCT (length W) and the column
+// DCT (length H) each run on the FFT kernels when the length has a plan, else
+// on the MFMA GEMM; the intermediate T[c][y][kx] (3, H, Kw) is shared.
+static int build_encode_plan(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
+                             const dctae_packing* pack, bool full, int ncb, bool want_raw, bool want_norm,
+                             const int64_t* tok_off_user, EncPlan& E) {
+  const int n = imgs->n_img;
+  const int P = cfg->patch_size, PP = P * P, S = cfg->max_seq_len;
+  int rc;
+  std::vector<ImgDesc> D(n);
+  std::vector<FftPlan> plans;
+  std::map<int, int> plan_idx;
+  auto plan_of = [&](int N) -> int {
+    auto it = plan_idx.find(N);
+    if (it != plan_idx.end()) return it->second;
+    FftPlan p;
+    int idx = -1;
+    if (fft_plan_for(ctx, N, P, &p) == 0 || bs_plan_for(ctx, N, &p) == 0) {
+      idx = (int)plans.size();
+      plans.push_back(p);
+    }
+    plan_idx[N] = idx;
+    return idx;
+  };
+  for (int i = 0; i < n; ++i) {
+    if ((rc = describe(ctx, cfg, imgs->hw[2 * i], imgs->hw[2 * i + 1], D[i]))) return rc;
+    D[i].rgb_off = imgs->img_off[i];
+    if (full) {
+      D[i].row = pack->row[i];
+      D[i].col = pack->col[i];
+      D[i].k = pack->k[i];
+      D[i].local_id = pack->local_id[i];
+      if (D[i].k < 1 || D[i].k > D[i].T || D[i].k > S)
+        return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": k out of range (FE:429-435)");
+      if (D[i].row < 0 || D[i].row >= pack->n_rows || D[i].col < 0 || D[i].col + D[i].k > S)
+        return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": packed span outside (rows, S)");
+    }
+    D[i].plan_w = plan_of(D[i].W);
+    D[i].plan_h = plan_of(D[i].H);
+    D[i].bs = (D[i].plan_w >= 0 && plans[D[i].plan_w].kind == 1 ? 1 : 0) |
+              (D[i].plan_h >= 0 && plans[D[i].plan_h].kind == 1 ? 2 : 0);
+    D[i].tperm = ctx->opt.tperm && D[i].plan_w < 0 && D[i].plan_h < 0;
+    // band layout: rows on k_rows512pk (Kw = 448) and columns on k_cols512b (Kh = 448)
+    D[i].tband = ctx->opt.cols512b && ctx->opt.rows_kernel == 4 && cfg->max_patch_w == 32 && cfg->max_patch_h == 32 &&
+                 D[i].H == 512 && D[i].W == 512 && D[i].Kh == 448 && D[i].Kw == 448 && D[i].bs == 0 && D[i].plan_w >= 0 &&
+                 plans[D[i].plan_w].spec == 1 && D[i].plan_h >= 0 && plans[D[i].plan_h].spec == 1;
+    // packed encodes of band images: item-major token staging (stage_pos; the
+    // staging is internal there, while dctae_spectrum_tokens hands it out in flat order)
+    if (full && D[i].tband) D[i].tband |= 2;
+  }
+  if (full)
+    for (int r = 0; r < pack->n_rows; ++r)
+      if (pack->row_len[r] < 0 || pack->row_len[r] > S) return fail(ctx, DCTAE_EINVAL, "row_len out of range");
+  // chunks: FFT images are grouped so the intermediate T of a chunk stays in
+  // the 256 MiB Infinity Cache between the row and column kernels
+  auto ws_of = [&](const ImgDesc& d) {
+    int64_t w = 3ll * d.Kw * d.H + 64;
+    if (d.plan_w < 0) w += 3ll * d.H * d.W + 64;
+    if (d.plan_h < 0 || (d.bs & 2)) w += 3ll * d.Kh * d.Kw + 64;
+    return w * 4;
+  };
+  auto st_of = [&](const ImgDesc& d) {
+    return (int64_t)d.T * (4 + 2 * ncb + (want_raw && full ? 4 * PP : 0) + (want_norm ? 4 * PP : 0));
+  };
+  for (int i = 0; i < n;) {
+    ChunkJob j{};
+    j.i0 = i;
+    int64_t wsb = 0;
+    while (i < n) {
+      const int64_t w = ws_of(D[i]);
+      const bool fft = D[i].plan_w >= 0 && D[i].plan_h >= 0;
+      const int64_t cap = fft ? std::min<int64_t>(ctx->opt.chunk_bytes, ctx->opt.ws_limit) : ctx->opt.ws_limit;
+      if (i > j.i0 && wsb + w > cap) break;
+      wsb += w;
+      ++i;
+    }
+    j.i1 = i;
+    E.jobs.push_back(j);
+  }
+  const int rows_cap = P * std::max(cfg->max_patch_h, cfg->max_patch_w);
+  std::vector<GemmProblem> probs;
+  int64_t tok = 0;
+  for (auto& j : E.jobs) {
+    int64_t wsf = 0;
+    j.max_T = 1;
+    j.max_hw = 1;
+    auto up = [](int64_t v) { return (v + 63) & ~63ll; };  // 256-byte aligned regions (float4 strip loads)
+    for (int i = j.i0; i < j.i1; ++i) {
+      ImgDesc& d = D[i];
+      if (ctx->opt.t_alias > 0 && i - j.i0 >= ctx->opt.t_alias) {   // profiling: T slots shared (wrong output)
+        d.ws_t = D[j.i0 + (i - j.i0) % ctx->opt.t_alias].ws_t;
+        d.ws_p = d.ws_y = wsf;
+        d.tok_off = full ? tok : tok_off_user[i];
+        tok += d.T;
+        j.max_T = std::max(j.max_T, d.T);
+        j.max_hw = std::max<int64_t>(j.max_hw, (int64_t)d.H * d.W);
+        continue;
+      }
+      d.ws_t = wsf;
+      wsf += up(3ll * d.Kw * d.H);
+      d.ws_p = wsf;
+      if (d.plan_w < 0) wsf += up(3ll * d.H * d.W);
+      d.ws_y = wsf;
+      if (d.plan_h < 0 || (d.bs & 2)) wsf += up(3ll * d.Kh * d.Kw);
+      d.tok_off = full ? tok : tok_off_user[i];
+      tok += d.T;
+      j.max_T = std::max(j.max_T, d.T);
+      j.max_hw = std::max<int64_t>(j.max_hw, (int64_t)d.H * d.W);
+    }
+    j.amax_off = wsf;
+    wsf += up(3ll * (j.i1 - j.i0) + 9);   // |max| pairs, then k_rows_fused's per-image flags, "any" word, 8 tile counters
+    E.ws_need = std::max<size_t>(E.ws_need, (size_t)wsf * 4);
+    E.max_T = std::max(E.max_T, j.max_T);
+  }
+  E.n_tok = tok;
+  E.n_img = n;
+  E.uniform = true;
+  for (int i = 1; i < n; ++i) E.uniform = E.uniform && D[i].H == D[0].H && D[i].W == D[0].W;
+  {
+    int64_t st = 0;
+    for (int i = 0; i < n; ++i) st += st_of(D[i]);
+    E.st_need = (size_t)st + 4096;
+  }
+  if ((rc = ensure_ws(ctx, std::max<size_t>(E.ws_need, 256), std::max<size_t>(E.st_need, 256)))) return rc;
+  float* ws = ctx->ws;
+  for (auto& j : E.jobs) {
+    j.desc_off = E.pb.add(D.data() + j.i0, j.i1 - j.i0);
+    const size_t p0 = probs.size();
+    std::vector<TileRef> rt, ct, ft;
+    std::vector<int2> fr[kVariants];
+    std::vector<int4> fc[kVariants];
+    std::vector<int2> br[4];
+    std::vector<int4> bc[4];
+    std::vector<int32_t> fold;
+    std::vector<int2> ipt;
+    std::vector<int32_t> pc, pb;
+    std::vector<int2> epi;
+    int pc_qw = 0;
+    bool pc_ok = cfg->max_patch_h <= 32;   // k_fft_cols7 keeps Kh <= 448 rows
+    j.lds_rows = j.lds_cols = 0;
+    for (int i = j.i0; i < j.i1; ++i) {
+      const ImgDesc& d = D[i];
+      const int li = i - j.i0;
+      if (d.plan_w < 0) {
+        // T[c][y][kx] = sum_x CW[kx][x] * IPT[c][y][x], folded: even kx over
+        // IPT[x] + IPT[W-1-x], odd kx over IPT[x] - IPT[W-1-x] (half the flops)
+        const size_t q0 = probs.size();
+        for (int par = 0; par < 2; ++par) {
+          const int M = par ? d.Kw / 2 : (d.Kw + 1) / 2, K = par ? d.W / 2 : (d.W + 1) / 2;
+          if (M == 0) continue;
+          const float* CW;
+          if ((rc = dct_matrix(ctx, d.W, std::min(d.W, rows_cap), &CW, par))) return rc;
+          // A: the folded IPT (k_rgb_to_ipt), u at x < ceil(W/2), v after it; B:
+          // the half DCT matrix (shared by the channels).  T rows y are the GEMM
+          // rows, so a wave's stores run along kx (the accumulator's lane-fast
+          // dimension; with the roles swapped they strided by Kw floats)
+          // parity-planar T (tperm: the columns are GEMMs too): each parity's
+          // outputs are contiguous runs (interleaved stores made every line
+          // twice-written: 4.4 GB of writes for 2.7 GB of T on config 4)
+          GemmProblem g = d.tperm ? gemm(ws + d.ws_p + (par ? (d.W + 1) / 2 : 0), (int64_t)d.H * d.W, d.W, 1, CW, 0,
+                                         K, 1, ws + d.ws_t + (par ? (d.Kw + 1) / 2 : 0), (int64_t)d.Kw * d.H, d.Kw,
+                                         1, d.H, M, K, 3)
+                                  : gemm(ws + d.ws_p + (par ? (d.W + 1) / 2 : 0), (int64_t)d.H * d.W, d.W, 1, CW, 0,
+                                         K, 1, ws + d.ws_t + par, (int64_t)d.Kw * d.H, d.Kw, 2, d.H, M, K, 3);
+          attach_x3(ctx, g);
+          uint32_t* am = reinterpret_cast<uint32_t*>(ws + j.amax_off) + 2 * li;
+          g.amax = am;                               // k_rgb_to_ipt's |max| of the folded IPT
+          g.omax = d.plan_h < 0 ? am + 1 : nullptr;  // T's |max| for the column GEMM
+          g.pad2 = li;                               // k_rows_fused: the image and the parity
+          g.pad3 = par;
+          probs.push_back(g);
+        }
+        // k_rows_fused (colour transform + folds + row GEMM in one pass) for the
+        // tperm images whose parity matrices are cached pre-split (both forms:
+        // the fix-up runs the bf16 one) and fit its 256 output columns
+        bool fz = ctx->opt.rows_fused && d.tperm && probs.size() == q0 + 2;   // both parities, consecutive
+        for (size_t q = q0; q < probs.size(); ++q) fz = fz && probs[q].Xh && probs[q].N <= fused_max_n();
+        if (fz)
+          for (int rb = 0; rb * fused_pairs_per_block() < (d.H + 1) / 2; ++rb) ft.push_back(TileRef{(int)(q0 - p0), rb});
+        else
+          for (size_t q = q0; q < probs.size(); ++q) add_tiles(rt, (int)(q - p0), probs[q]);
+        if (fz) {
+          j.any_fused = 1;
+        } else {
+          j.any_gemm_rows = 1;
+          // k_rgb_to_ipt's (x, y)-mirrored pixel groups of this image
+          const int64_t ng = (int64_t)(d.plan_h < 0 ? (d.H + 1) / 2 : d.H) * ((d.W + 1) / 2);
+          for (int64_t g0 = 0; g0 < ng; g0 += rgb_to_ipt_groups_per_block()) ipt.push_back(make_int2(li, (int)g0));
+        }
+      } else if (d.bs & 1) {
+        const int L = plans[d.plan_w].bs_L, rpb = bs_rows_per_block(L);
+        for (int y0 = 0; y0 < d.H; y0 += rpb) br[bs_lidx(L)].push_back(make_int2(li, y0));
+      } else {
+        const FftPlan& p = plans[d.plan_w];
+        for (int y0 = 0; y0 < d.H; y0 += p.rows_per_block) fr[p.spec].push_back(make_int2(li, y0));
+        if (p.spec) {
+          j.tw_off[p.spec] = p.tw_off;
+          j.post_off_r[p.spec] = p.post_off;
+        } else {
+          j.lds_rows = std::max<size_t>(j.lds_rows, (size_t)2 * p.rows_per_block * 3 * (2 * p.M + 1) * 4);
+        }
+      }
+      if (d.plan_h < 0 || (d.bs & 2))   // Y in the workspace: the tile epilogue's (tile row, channel) blocks
+        for (int h = 0; h < d.qh; ++h)
+          for (int c = 0; c < 3; ++c) epi.push_back(make_int2(li, 3 * h + c));
+      if (d.plan_h < 0) {
+        // Y[c][ky][kx] = sum_y CH[ky][y] * T[c][y][kx], folded along y as the rows
+        for (int par = 0; par < 2; ++par) {
+          const int M = par ? d.Kh / 2 : (d.Kh + 1) / 2, K = par ? d.H / 2 : (d.H + 1) / 2;
+          if (M == 0) continue;
+          const float* CH;
+          if ((rc = dct_matrix(ctx, d.H, std::min(d.H, rows_cap), &CH, par))) return rc;
+          // B: T folded along y (by the row GEMM of the y-folded IPT, or in place by
+          // k_fold_t after FFT rows): u in rows m < ceil(H/2), v[m] in row H-1-m
+          GemmProblem g = gemm(CH, 0, K, 1, ws + d.ws_t + (par ? (int64_t)(d.H - 1) * d.Kw : 0),
+                               (int64_t)d.Kw * d.H, 1, par ? -(int64_t)d.Kw : d.Kw,
+                               ws + d.ws_y + (int64_t)par * d.Kw, (int64_t)d.Kh * d.Kw, 2 * (int64_t)d.Kw, 1, M,
+                               d.Kw, K, 3);
+          attach_x3(ctx, g);
+          g.amax = reinterpret_cast<uint32_t*>(ws + j.amax_off) + 2 * li + 1;   // T's |max| (row GEMM / k_fold_t)
+          add_tiles(ct, (int)(probs.size() - p0), g);
+          probs.push_back(g);
+        }
+        j.any_gemm_cols = 1;
+        if (d.plan_w >= 0) {
+          j.fold_t = 1;
+          fold.push_back(li);
+          j.fold_max_hw = std::max<int64_t>(j.fold_max_hw, (int64_t)d.H * d.W);
+        }
+      } else if (d.bs & 2) {
+        const int L = plans[d.plan_h].bs_L, cpb = bs_cols_per_block(L);
+        for (int c = 0; c < 3; ++c)
+          for (int kx0 = 0; kx0 < d.Kw; kx0 += cpb) bc[bs_lidx(L)].push_back(make_int4(li, c, kx0, 0));
+        j.any_bs_cols = 1;
+      } else if (d.tband) {
+        pb.push_back(li);
+        j.tw_off_c[1] = plans[d.plan_h].tw_off;
+        j.post_off_c[1] = plans[d.plan_h].post_off;
+      } else {
+        const FftPlan& p = plans[d.plan_h];
+        // generic kernel: one tile column per block; specialised: groups of
+        // up to 16 adjacent tile columns walked by one block
+        const int G = 1;
+        for (int c = 0; c < 3; ++c)
+          for (int w = 0; w < d.qw; w += G) fc[p.spec].push_back(make_int4(li, c, w, std::min(G, d.qw - w)));
+        if (p.spec == 1) {
+          pc_ok = pc_ok && (pc.empty() || d.qw == pc_qw);
+          pc_qw = d.qw;
+          pc.push_back(li);
+        }
+        if (p.spec) {
+          j.tw_off_c[p.spec] = p.tw_off;
+          j.post_off_c[p.spec] = p.post_off;
+        } else {
+          j.lds_cols = std::max<size_t>(j.lds_cols, (size_t)2 * 2 * p.M * P * 4);
+        }
+      }
+    }
+    // k_gemm_h2 when every GEMM of the job has its shared matrix pre-split
+    j.h2 = ctx->opt.gemm_x3 && ctx->opt.gemm_h2 && probs.size() > p0;
+    for (size_t q = p0; q < probs.size(); ++q) j.h2 = j.h2 && probs[q].Xh != nullptr;
+    j.gp_off = E.pb.add(probs.data() + p0, probs.size() - p0);
+    if (ctx->opt.xcd_order) {
+      xcd_deal_tiles(rt, probs.data() + p0, 1);
+      xcd_deal_tiles(ct, probs.data() + p0, 2);
+      xcd_deal_tiles(ft, probs.data() + p0, 1);   // an image's blocks on one XCD: its two matrices in one L2
+    }
+    j.rows_t_off = E.pb.add(rt.data(), rt.size());
+    j.fused_t_off = E.pb.add(ft.data(), ft.size());
+    j.n_fused_tiles = (int)ft.size();
+    j.cols_t_off = E.pb.add(ct.data(), ct.size());
+    // XCD-aware order of the column blocks (speed only; any order is correct):
+    // blocks b and b+8 are dealt to the same XCD, so give all the blocks of
+    // one (image, channel) the same b % 8 and consecutive b / 8 — the 56-byte
+    // row slices of neighbouring tile columns then share that XCD's L2 lines.
+    if (ctx->opt.xcd_order) {
+      for (int v = 1; v < kVariants; ++v) {
+        std::vector<int4>& L = fc[v];
+        if (L.size() < 16) continue;
+        // units = runs of blocks with the same (image, channel), in list order
+        std::vector<std::pair<size_t, size_t>> units;
+        for (size_t a0 = 0; a0 < L.size();) {
+          size_t a1 = a0 + 1;
+          while (a1 < L.size() && L[a1].x == L[a0].x && L[a1].y == L[a0].y) ++a1;
+          units.push_back({a0, a1});
+          a0 = a1;
+        }
+        std::vector<std::vector<int4>> lanes(8);
+        for (size_t u = 0; u < units.size(); ++u)
+          for (size_t a = units[u].first; a < units[u].second; ++a) lanes[u % 8].push_back(L[a]);
+        std::vector<int4> out;
+        out.reserve(L.size());
+        size_t maxlen = 0;
+        for (auto& l : lanes) maxlen = std::max(maxlen, l.size());
+        for (size_t q = 0; q < maxlen; ++q)
+          for (int x = 0; x < 8; ++x)
+            if (q < lanes[x].size()) out.push_back(lanes[x][q]);
+        L.swap(out);
+      }
+    }
+    for (int v = 0; v < kVariants; ++v) {
+      j.fr_off[v] = E.pb.add(fr[v].data(), fr[v].size());
+      j.fc_off[v] = E.pb.add(fc[v].data(), fc[v].size());
+      j.n_fr[v] = (int)fr[v].size();
+      j.n_fc[v] = (int)fc[v].size();
+    }
+    j.ipt_off = E.pb.add(ipt.data(), ipt.size());
+    j.n_ipt = (int)ipt.size();
+    j.fold_off = E.pb.add(fold.data(), fold.size());
+    j.n_fold = (int)fold.size();
+    for (int l = 0; l < 4; ++l) {
+      j.br_off[l] = E.pb.add(br[l].data(), br[l].size());
+      j.bc_off[l] = E.pb.add(bc[l].data(), bc[l].size());
+      j.n_br[l] = (int)br[l].size();
+      j.n_bc[l] = (int)bc[l].size();
+    }
+    j.n_rows_tiles = (int)rt.size();
+    j.n_cols_tiles = (int)ct.size();
+    // all spec-1 column items of the job in one persistent launch, when their qw agree
+    j.n_pc = (pc_ok && (int)pc.size() * 3 * pc_qw == (int)fc[1].size()) ? (int)pc.size() : 0;
+    j.pc_qw = pc_qw;
+    j.pc_off = E.pb.add(pc.data(), pc.size());
+    j.n_pb = (int)pb.size();
+    j.pb_off = E.pb.add(pb.data(), pb.size());
+    j.n_epi = (int)epi.size();
+    j.epi_off = E.pb.add(epi.data(), epi.size());
+  }
+  E.plans_off = E.pb.add(plans.data(), plans.size());
+  E.all_desc_off = E.pb.add(D.data(), D.size());
+  if (full && pack->n_rows > 0) E.rowlen_off = E.pb.add(pack->row_len, pack->n_rows);
+  E.any_pad = false;
+  if (full)
+    for (int r = 0; r < pack->n_rows; ++r) E.any_pad = E.any_pad || pack->row_len[r] < S;
+  E.ncb = ncb;
+  return 0;
+}
+
+// One encode call: its arguments and what they ask for.
+struct EncCall {
+  const dctae_fe_cfg* cfg;
+  const dctae_images* imgs;
+  const dctae_packing* pack;   // NULL: token mode
+  const dctae_norm* norm;
+  const dctae_lfq* lfq;
+  const dctae_packed_out* out;
+  const int64_t* tok_off_user;   // token mode: the caller's token offsets
+  float *tokens_dev, *scores_dev;
+  const float *proj_w, *proj_b;   // fused LFQ projections (dctae_encode_lfq_proj)
+  // set by check()
+  bool full, want_codes, want_raw, want_norm;
+  int ncb;
+  int check(dctae_ctx* ctx);
+  std::vector<int64_t> plan_key(const Options& opt) const;
+};
+
+int EncCall::check(dctae_ctx* ctx) {
+  int rc = check_cfg(ctx, cfg);
+  if (rc) return rc;
+  if (!imgs || imgs->n_img < 0 || (imgs->n_img > 0 && (!imgs->rgb_dev || !imgs->img_off || !imgs->hw)))
+    return fail(ctx, DCTAE_EINVAL, "bad image descriptor");
+  full = (pack != nullptr);
+  const int n = imgs->n_img;
+  const int P = cfg->patch_size, PP = P * P;
+  want_codes = full && out && out->codes_dev;
+  if (full) {
+    if (!out || !out->positions_dev || !out->channels_dev || !out->image_ids_dev || !out->key_pad_dev)
+      return fail(ctx, DCTAE_EINVAL, "packed outputs positions/channels/image_ids/key_pad are required");
+    if ((want_codes || out->patches_dev) && !norm) return fail(ctx, DCTAE_EINVAL, "codes/patches need PatchNorm tables");
+    if (want_codes && !proj_w && (rc = check_lfq(ctx, lfq, PP))) return rc;
+    if (proj_w && (!want_codes || !lfq || lfq->codebook_dim < 1 || lfq->codebook_dim > 16 ||
+                   lfq->num_codebooks < 1 || lfq->num_codebooks > 64 || PP % 4 != 0 ||
+                   lfq->codebook_dim * lfq->num_codebooks > 256 || ((uintptr_t)proj_w & 15)))
+      return fail(ctx, DCTAE_EUNSUP, "fused LFQ projections: codes output, codebook_dim <= 16, ncb * cd <= 256, "
+                                     "P*P % 4 == 0, 16-byte aligned weights");
+    if (pack->n_rows < 0 || (n > 0 && (!pack->row || !pack->col || !pack->k || !pack->local_id)) ||
+        (pack->n_rows > 0 && !pack->row_len))
+      return fail(ctx, DCTAE_EINVAL, "bad packing descriptor");
+  }
+  if (norm && (!norm->median_dev || !norm->b_dev)) return fail(ctx, DCTAE_EINVAL, "PatchNorm tables are NULL");
+  ncb = want_codes ? lfq->num_codebooks : 0;
+  want_raw = (full && out->raw_patches_dev) || (!full && tokens_dev);
+  // LFQ with projections: the column epilogues stage the PatchNorm output,
+  // dctae_lfq_project_in turns the staged tokens into staged u16 codes, and the
+  // sort / pack gathers those as usual
+  want_norm = full && (out->patches_dev || proj_w);
+  return 0;
+}
+
+// plan cache key: every input that shapes the launch sequence (the workspace
+// pointer is compared beside it: dctae_ctx::enc_ws)
+std::vector<int64_t> EncCall::plan_key(const Options& opt) const {
+  const int n = imgs->n_img;
+  std::vector<int64_t> key;
+  key.reserve(32 + 6ll * n + (full ? pack->n_rows : 0));
+  key.insert(key.end(), {(int64_t)full, n, cfg->patch_size, cfg->max_patch_h, cfg->max_patch_w, cfg->max_seq_len, ncb,
+                         (int64_t)want_raw, (int64_t)want_norm});
+  push_plan_options(opt, key);
+  for (int i = 0; i < n; ++i) {
+    key.push_back(imgs->img_off[i]);
+    key.push_back(((int64_t)imgs->hw[2 * i] << 32) | (uint32_t)imgs->hw[2 * i + 1]);
+    if (full) {
+      key.push_back(((int64_t)pack->row[i] << 32) | (uint32_t)pack->col[i]);
+      key.push_back(((int64_t)pack->k[i] << 32) | (uint32_t)pack->local_id[i]);
+    } else {
+      key.push_back(tok_off_user[i]);
+    }
+  }
+  if (full) {
+    key.push_back(pack->n_rows);
+    for (int r = 0; r < pack->n_rows; ++r) key.push_back(pack->row_len[r]);
+  }
+  return key;
+}
+
+// the call's plan: the cached one, or a new one that replaces it
+static int encode_plan(dctae_ctx* ctx, const EncCall& c, EncPlan** out) {
+  std::vector<int64_t> key = c.plan_key(ctx->opt);
+  if (!ctx->enc_plan || ctx->enc_ws != ctx->ws || key != ctx->enc_key) {
+    EncPlan* E = new EncPlan();
+    E->id = ++ctx->plan_counter;
+    int rc = build_encode_plan(ctx, c.cfg, c.imgs, c.pack, c.full, c.ncb, c.want_raw, c.want_norm, c.tok_off_user, *E);
+    if (rc) {
+      delete E;
+      return rc;
+    }
+    delete ctx->enc_plan;
+    ctx->enc_plan = E;
+    ctx->enc_key = std::move(key);
+    ctx->enc_ws = ctx->ws;   // the plan holds workspace addresses, and ensure_ws may have moved it
+  }
+  *out = ctx->enc_plan;
+  return 0;
+}
+
+void dctae::drop_encode_plan(dctae_ctx* ctx) {
+  delete ctx->enc_plan;
+  ctx->enc_plan = nullptr;
+}
+
+static PackSinks pack_sinks(const dctae_packed_out* out) {
+  PackSinks ps{};
+  ps.codes = out->codes_dev;
+  ps.pos = out->positions_dev;
+  ps.ch = out->channels_dev;
+  ps.ids = out->image_ids_dev;
+  ps.patches = out->patches_dev;
+  ps.raw = out->raw_patches_dev;
+  ps.scores = out->scores_dev;
+  ps.key_pad = out->key_pad_dev;
+  return ps;
+}
+
+// token staging for the whole call (flat token order, global offsets)
+static TokenSinks token_sinks(const dctae_ctx* ctx, const EncCall& c, const EncPlan& E) {
+  TokenSinks sk{};
+  if (!c.full) {
+    sk.scores = c.scores_dev;
+    sk.raw = c.tokens_dev;
+    return sk;
+  }
+  const int PP = c.cfg->patch_size * c.cfg->patch_size;
+  const int64_t nt = E.n_tok;
+  uint8_t* st = ctx->stage;
+  sk.scores = (float*)st;
+  st += ((nt * 4 + 255) & ~255ll);
+  if (c.ncb) {
+    sk.codes = (uint16_t*)st;
+    st += ((nt * 2 * c.ncb + 255) & ~255ll);
+  }
+  if (c.want_norm) {
+    sk.norm = (float*)st;
+    st += nt * 4 * PP;
+  }
+  if (c.out->raw_patches_dev) {
+    sk.raw = (float*)st;
+    st += nt * 4 * PP;
+  }
+  return sk;
+}
+
+// The context's side stream for the length of one call.  fork(s) lets the side
+// stream start after what `s` holds so far; once forked, `s` waits for the side
+// stream at join() and on every exit (error returns included), so the next
+// call's order_after_previous covers it before the workspace is reused.
+struct SideStream {
+  dctae_ctx* ctx;
+  hipStream_t s = nullptr;
+  bool armed = false;
+  explicit SideStream(dctae_ctx* c) : ctx(c) {}
+  int ensure() {
+    if (ctx->side) return 0;
+    if (hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&ctx->side_in, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&ctx->side_out, hipEventDisableTiming) != hipSuccess)
+      return fail(ctx, DCTAE_EHIP, "side stream allocation failed");
+    return 0;
+  }
+  int fork(hipStream_t from) {
+    HIPCHK(ctx, hipEventRecord(ctx->side_in, from));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->side_in, 0));
+    s = from;
+    armed = true;
+    return 0;
+  }
+  void join() {
+    if (!armed) return;
+    armed = false;
+    if (hipEventRecord(ctx->side_out, ctx->side) != hipSuccess || hipStreamWaitEvent(s, ctx->side_out, 0) != hipSuccess)
+      hipStreamSynchronize(ctx->side);
+  }
+  ~SideStream() { join(); }
+};
+
+// What the launches of one call share, and the pieces of its launch sequence.
+struct EncLaunch {
+  dctae_ctx* ctx;
+  const dctae_fe_cfg* cfg;
+  const dctae_images* imgs;
+  const EncPlan& E;
+  hipStream_t s;             // the caller's stream
+  uint8_t* pd;               // the uploaded plan
+  const FftPlan* plans_d;
+  const ImgDesc* all_d;      // every image of the call (sort / pack)
+  EncParams epj;             // the column epilogues' parameters
+  TokenSinks sk, skc;        // the call's staging; the column kernels' sinks
+  EncParams eps;             // the pack's parameters
+  PackSinks ps;
+
+  void gemm(const ChunkJob& j, size_t tiles_off, int n_tiles, hipStream_t st, int share) const {
+    if (j.h2)
+      launch_gemm_h2((const GemmProblem*)(pd + j.gp_off), (const TileRef*)(pd + tiles_off), n_tiles, st, share,
+                     ctx->opt.gemm_dma != 0, ctx->opt.cols_dma != 0);
+    else
+      ctx_gemm(ctx, 3, (const GemmProblem*)(pd + j.gp_off), (const TileRef*)(pd + tiles_off), n_tiles, st, share);
+  }
+
+  // row half of a chunk job on a stream
+  void do_rows(const ChunkJob& j, hipStream_t st) const {
+    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
+    uint32_t* amax = reinterpret_cast<uint32_t*>(ctx->ws + j.amax_off);
+    if (j.h2 || j.any_fused) hipMemsetAsync(amax, 0, 12 * (size_t)(j.i1 - j.i0) + 36, st);   // errors surface at hipGetLastError
+    if (j.any_fused) {
+      int* flags = reinterpret_cast<int*>(amax + 2 * (j.i1 - j.i0));
+      {
+        Timer t(ctx, st, "rows_fused");
+        launch_rows_fused((const GemmProblem*)(pd + j.gp_off), (const TileRef*)(pd + j.fused_t_off), j.n_fused_tiles,
+                          dd, imgs->rgb_dev, ctx->cm, amax, flags, j.i1 - j.i0, st, false);
+      }
+      Timer t(ctx, st, "rows_fixup");
+      launch_rows_fused((const GemmProblem*)(pd + j.gp_off), (const TileRef*)(pd + j.fused_t_off), j.n_fused_tiles, dd,
+                        imgs->rgb_dev, ctx->cm, amax, flags, j.i1 - j.i0, st, true);
+    }
+    if (j.any_gemm_rows) {
+      {
+        Timer t(ctx, st, "rgb_to_ipt");
+        launch_rgb_to_ipt(dd, (const int2*)(pd + j.ipt_off), j.n_ipt, imgs->rgb_dev, ctx->ws, ctx->cm,
+                          j.h2 ? amax : nullptr, st);
+      }
+      Timer t(ctx, st, "gemm_rows");
+      gemm(j, j.rows_t_off, j.n_rows_tiles, st, 1);
+    }
+    for (int l = 0; l < 4; ++l)
+      if (j.n_br[l]) {
+        Timer t(ctx, st, "bs_rows");
+        launch_bs_rows(kBsL[l], dd, plans_d, (const int2*)(pd + j.br_off[l]), j.n_br[l], imgs->rgb_dev, ctx->ws,
+                       ctx->fft_tab, ctx->cm, st, ctx->opt.bs_ablate);
+      }
+    if (j.n_fr[0]) {
+      Timer t(ctx, st, "fft_rows");
+      launch_fft_rows(dd, plans_d, (const int2*)(pd + j.fr_off[0]), j.n_fr[0], j.lds_rows, imgs->rgb_dev, ctx->ws,
+                      ctx->fft_tab, ctx->cm, st);
+    }
+    for (int v = 1; v < kVariants; ++v)
+      if (j.n_fr[v]) {
+        Timer t(ctx, st, "fft_rows");
+        if (v == 1 && ctx->opt.rows_kernel == 4 && cfg->max_patch_w == 32)
+          launch_rows512(dd, (const int2*)(pd + j.fr_off[v]), j.n_fr[v], imgs->rgb_dev, ctx->ws,
+                         ctx->fft_tab + j.tw_off[v], ctx->fft_tab + j.post_off_r[v], ctx->cm, st);
+        else
+          launch_fft_rows_spec(v, dd, (const int2*)(pd + j.fr_off[v]), j.n_fr[v], imgs->rgb_dev, ctx->ws,
+                               ctx->fft_tab + j.tw_off[v], ctx->fft_tab + j.post_off_r[v], ctx->cm, st);
+      }
+  }
+
+  // column half of a chunk job on a stream
+  void do_cols(const ChunkJob& j, hipStream_t st) const {
+    const int nj = j.i1 - j.i0;
+    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
+    if (j.any_gemm_cols) {
+      if (j.fold_t) {
+        Timer t(ctx, st, "fold_t");
+        launch_fold_t(dd, (const int32_t*)(pd + j.fold_off), j.n_fold, j.fold_max_hw, ctx->ws,
+                      j.h2 ? reinterpret_cast<uint32_t*>(ctx->ws + j.amax_off) : nullptr, st);
+      }
+      Timer t(ctx, st, "gemm_cols");
+      gemm(j, j.cols_t_off, j.n_cols_tiles, st, 2);
+    }
+    for (int l = 0; l < 4; ++l)
+      if (j.n_bc[l]) {
+        Timer t(ctx, st, "bs_cols");
+        launch_bs_cols(kBsL[l], dd, plans_d, (const int4*)(pd + j.bc_off[l]), j.n_bc[l], ctx->ws, ctx->fft_tab, st,
+                       ctx->opt.bs_ablate);
+      }
+    if (j.any_gemm_cols || j.any_bs_cols) {
+      Timer t(ctx, st, "tile_epilogue");
+      launch_tile_epilogue(dd, nj, j.max_T, ctx->ws, epj, skc, st, (const int2*)(pd + j.epi_off), j.n_epi);
+    }
+    if (j.n_fc[0]) {
+      Timer t(ctx, st, "fft_cols");
+      launch_fft_cols(dd, plans_d, (const int4*)(pd + j.fc_off[0]), j.n_fc[0], j.lds_cols, ctx->ws, ctx->fft_tab,
+                      epj, skc, st);
+    }
+    if (j.n_pb) {
+      Timer t(ctx, st, "fft_cols");
+      launch_cols512b(dd, (const int*)(pd + j.pb_off), j.n_pb, ctx->ws, ctx->fft_tab + j.tw_off_c[1],
+                      ctx->fft_tab + j.post_off_c[1], epj, skc, st, ctx->opt.cols_wide != 0);
+    }
+    for (int v = 1; v < kVariants; ++v)
+      if (j.n_fc[v]) {
+        Timer t(ctx, st, "fft_cols");
+        launch_fft_cols_spec(v, dd, (const int4*)(pd + j.fc_off[v]), j.n_fc[v], ctx->ws, ctx->fft_tab + j.tw_off_c[v],
+                             ctx->fft_tab + j.post_off_c[v], epj, skc, st,
+                             v == 1 && j.n_pc ? (const int*)(pd + j.pc_off) : nullptr, v == 1 ? j.n_pc : 0, j.pc_qw);
+      }
+  }
+
+  // sort / pack of images [a, a + m) on a stream
+  void sort_pack(int a, int m, hipStream_t st) const {
+    launch_sort_pack(all_d + a, m, next_pow2(E.max_T), eps, sk, ps, st, ctx->opt.sort_kernel, E.max_T);
+  }
+
+  // halves (option): see Options::halves.  The plan kernel variant (>= 2) of
+  // a call that qualifies, else 0.
+  int halves_variant() const {
+    if (E.jobs.size() != 1 || !E.uniform || E.n_img < 32) return 0;
+    const ChunkJob& j = E.jobs[0];
+    bool ok = !j.any_gemm_rows && !j.any_gemm_cols && !j.any_bs_cols && j.n_pb == 0 && j.n_pc == 0 && j.n_fr[0] == 0 &&
+              j.n_fc[0] == 0;
+    for (int l = 0; l < 4; ++l) ok = ok && !j.n_br[l] && !j.n_bc[l];
+    int vv = -1;
+    for (int v = 1; v < kVariants; ++v)
+      if (j.n_fr[v] || j.n_fc[v]) {
+        if (vv < 0 && j.n_fr[v] && j.n_fc[v]) vv = v;
+        else ok = false;
+      }
+    return ok && vv >= 2 && j.n_fr[vv] % E.n_img == 0 && j.n_fc[vv] % E.n_img == 0 ? vv : 0;
+  }
+
+  // the halves schedule on plan kernel variant hv; *sorted0 = the images it packed
+  int run_halves(int hv, SideStream& side, int* sorted0) const {
+    const ChunkJob& j = E.jobs[0];
+    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
+    const int n_img = E.n_img, h = n_img / 2;
+    const int rpi = j.n_fr[hv] / n_img, cpi = j.n_fc[hv] / n_img;   // blocks / items per image (image-major lists)
+    const int2* rl = (const int2*)(pd + j.fr_off[hv]);
+    const int4* cl = (const int4*)(pd + j.fc_off[hv]);
+    auto rows = [&](int a, int m, hipStream_t st) {
+      Timer t(ctx, st, "fft_rows");
+      launch_fft_rows_spec(hv, dd, rl + (size_t)a * rpi, m * rpi, imgs->rgb_dev, ctx->ws, ctx->fft_tab + j.tw_off[hv],
+                           ctx->fft_tab + j.post_off_r[hv], ctx->cm, st);
+    };
+    auto cols = [&](int a, int m, hipStream_t st) {
+      Timer t(ctx, st, "fft_cols");
+      launch_fft_cols_spec(hv, dd, cl + (size_t)a * cpi, m * cpi, ctx->ws, ctx->fft_tab + j.tw_off_c[hv],
+                           ctx->fft_tab + j.post_off_c[hv], epj, skc, st, nullptr, 0, 0);
+    };
+    rows(0, h, s);
+    if (int rc = side.fork(s)) return rc;
+    cols(0, h, ctx->side);
+    {
+      Timer t(ctx, ctx->side, "sort_pack");
+      sort_pack(0, h, ctx->side);
+    }
+    rows(h, n_img - h, s);
+    cols(h, n_img - h, s);
+    *sorted0 = h;
+    return 0;
+  }
+
+  // sort_overlap: one job of band images only -> columns in two halves, the
+  // first half's sort / pack on the side stream while the second half's
+  // columns run (the sort is latency-bound, the column kernel issue-bound)
+  int run_split_cols(const ChunkJob& j, SideStream& side, int* sorted0) const {
+    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
+    const int* list = (const int*)(pd + j.pb_off);
+    const int h = j.n_pb / 2;
+    {
+      Timer t(ctx, s, "fft_cols");
+      launch_cols512b(dd, list, h, ctx->ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1], epj, skc, s,
+                      ctx->opt.cols_wide != 0);
+    }
+    if (int rc = side.fork(s)) return rc;
+    sort_pack(0, h, ctx->side);
+    {
+      Timer t(ctx, s, "fft_cols");
+      launch_cols512b(dd, list + h, j.n_pb - h, ctx->ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1],
+                      epj, skc, s, ctx->opt.cols_wide != 0);
+    }
+    *sorted0 = h;
+    return 0;
+  }
+
+#ifdef DCTAE_PROFILING
+  bool gate_applies() const {
+    return ctx->opt.gate && E.jobs.size() == 1 && E.n_img >= 2 && E.jobs[0].n_pb == E.n_img &&
+           E.jobs[0].n_fr[1] % E.n_img == 0 && ctx->opt.rows_kernel == 4;
+  }
+
+  // the profiling gate (Options::gate): part of the band path; *sorted0 = the images to leave unpacked
+  int run_gate(SideStream& side, int* sorted0) const {
+    const ChunkJob& j = E.jobs[0];
+    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
+    const int n_img = E.n_img, h = n_img / 2, rpi = j.n_fr[1] / n_img;
+    const int2* rl = (const int2*)(pd + j.fr_off[1]);
+    const int* cl = (const int*)(pd + j.pb_off);
+    auto rows = [&](int a, int m, hipStream_t st) {
+      Timer t(ctx, st, "fft_rows");
+      launch_rows512(dd, rl + (size_t)a * rpi, m * rpi, imgs->rgb_dev, ctx->ws, ctx->fft_tab + j.tw_off[1],
+                     ctx->fft_tab + j.post_off_r[1], ctx->cm, st);
+    };
+    auto cols = [&](int a, int m, hipStream_t st) {
+      Timer t(ctx, st, "fft_cols");
+      launch_cols512b(dd, cl + a, m, ctx->ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1], epj, skc,
+                      st, false);
+    };
+    const int64_t gate = ctx->opt.gate;
+    if (int rc = side.ensure()) return rc;
+    switch (gate) {
+      case 1: rows(0, n_img, s); break;
+      case 2: cols(0, n_img, s); break;
+      case 3:
+      case 4:
+        if (gate == 4) rows(0, h, s);
+        if (int rc = side.fork(s)) return rc;
+        cols(0, h, ctx->side);
+        rows(h, n_img - h, s);
+        side.join();
+        if (gate == 4) cols(h, n_img - h, s);
+        break;
+      case 5: rows(h, n_img - h, s); break;
+      case 6: cols(0, h, s); break;
+    }
+    *sorted0 = gate == 4 ? 0 : E.n_img;
+    return 0;
+  }
+#endif
+};
+
+static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
+                       const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
+                       const dctae_packed_out* out, const int64_t* tok_off_user, float* tokens_dev,
+                       float* scores_dev, hipStream_t s, const float* proj_w = nullptr,
+                       const float* proj_b = nullptr) {
+  EncCall c{cfg, imgs, pack, norm, lfq, out, tok_off_user, tokens_dev, scores_dev, proj_w, proj_b};
+  int rc = c.check(ctx);
+  if (rc) return rc;
+  const bool full = c.full;
+  EncPlan* plan;
+  if ((rc = encode_plan(ctx, c, &plan))) return rc;
+  const EncPlan& E = *plan;
+  if (proj_w && E.any_pad)
+    return fail(ctx, DCTAE_EUNSUP, "fused LFQ projections need rows without padding (the pad token's codes)");
+  order_after_previous(ctx, s);
+  if ((rc = upload_plan(ctx, E.pb, s, E.id))) return rc;
+  uint8_t* pd = ctx->plan_dev;
+
+  EncParams ep = enc_params(cfg, norm, c.want_codes && !proj_w ? lfq : nullptr);
+  if (norm && !c.want_norm) ep.thr = norm->thr_dev;
+  EncLaunch L{ctx, cfg, imgs, E, s, pd, (const FftPlan*)(pd + E.plans_off), (const ImgDesc*)(pd + E.all_desc_off)};
+  L.epj = ep;
+  if (!full) L.epj.median = nullptr;
+  // the pack's parameters (the projection kernel stages raw sign bits: the pack maps them, lfq_index_bits)
+  L.eps = ep;
+  if (proj_w) {
+    L.eps.ncb = lfq->num_codebooks;
+    L.eps.cb_dim = lfq->codebook_dim;
+    uint64_t pos, neg;
+    lfq_index_masks(lfq->codebook_scale, lfq->codebook_dim, &pos, &neg);
+    L.eps.code_pos = (uint32_t)pos;
+    L.eps.code_neg = (uint32_t)neg;
+  }
+  if (full) {
+    L.ps = pack_sinks(out);
+    // rows filled to max_seq_len (e.g. one 512^2 image per row) have no pads:
+    // the sort kernel writes their key_pad zeros, no k_pad_fill launch
+    if (pack->n_rows > 0 && E.any_pad) {
+      Timer t(ctx, s, "pad_fill");
+      launch_pad_fill((const int32_t*)(pd + E.rowlen_off), pack->n_rows, ep, out->key_pad_dev, L.ps, s);
+    }
+  }
+  L.sk = token_sinks(ctx, c, E);
+  L.skc = L.sk;   // the column kernels' sinks (codes come from the projection kernel)
+  if (proj_w) L.skc.codes = nullptr;
+
+  // the two-stream schedules apply to packed encodes without fused projections
+  SideStream side(ctx);
+  const bool two = full && !proj_w;
+  const bool split = two && ctx->opt.sort_overlap && E.jobs.size() == 1 && E.n_img >= 64 &&
+                     E.jobs[0].n_pb == E.n_img && E.jobs[0].i0 == 0;
+  const int hv = two && ctx->opt.halves && !split ? L.halves_variant() : 0;
+  if ((split || hv) && (rc = side.ensure())) return rc;
+  int sorted0 = 0;   // images [0, sorted0) need no sort / pack on the caller's stream
+  bool whole = false;   // the call's rows and columns are launched
+  if (hv) {
+    if ((rc = L.run_halves(hv, side, &sorted0))) return rc;
+    whole = true;
+  }
+#ifdef DCTAE_PROFILING
+  if (two && !hv && !split && L.gate_applies()) {
+    if ((rc = L.run_gate(side, &sorted0))) return rc;
+    whole = true;
+  }
+#endif
+  for (const ChunkJob& j : E.jobs) {
+    if (whole) break;
+    L.do_rows(j, s);
+    if (!split)
+      L.do_cols(j, s);
+    else if ((rc = L.run_split_cols(j, side, &sorted0)))
+      return rc;
+  }
+  if (proj_w && E.n_tok > 0) {
+    Timer t(ctx, s, "lfq_project_in");
+    const int PP = cfg->patch_size * cfg->patch_size;
+    if ((rc = proj_scratch(ctx, lfq->codebook_dim * lfq->num_codebooks, PP))) return rc;
+    // the staged tokens are PatchNorm outputs, clamped to [min_val, max_val]
+    // (patchnorm.py:163): the fp16 projection's operand bound
+    const float xb = ctx->opt.gemm_h2 ? std::max(std::fabs(norm->min_val), std::fabs(norm->max_val)) : 0.0f;
+    launch_lfq_project_in16(L.sk.norm, E.n_tok, PP, proj_w, proj_b, lfq->codebook_dim, lfq->num_codebooks, L.sk.codes,
+                            ctx->proj_ws, s, xb, ctx->opt.lfq_ws != 0);
+  }
+  if (full && E.n_img > sorted0) {
+    Timer t(ctx, s, "sort_pack");
+    L.sort_pack(sorted0, E.n_img - sorted0, s);
+  }
+  side.join();   // every output complete on the caller's stream
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+extern "C" {
+
+int dctae_encode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const dctae_packing* pack,
+                 const dctae_norm* norm, const dctae_lfq* lfq, const dctae_packed_out* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (!pack) return fail(ctx, DCTAE_EINVAL, "packing descriptor is NULL");
+  hipSetDevice(ctx->device);
+  return encode_impl(ctx, cfg, imgs, pack, norm, lfq, out, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int dctae_encode_lfq_proj(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
+                          const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
+                          const float* w_in_dev, const float* b_in_dev, const dctae_packed_out* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (!pack) return fail(ctx, DCTAE_EINVAL, "packing descriptor is NULL");
+  if (!w_in_dev || !out || !out->codes_dev) return fail(ctx, DCTAE_EINVAL, "project_in weight and codes output required");
+  hipSetDevice(ctx->device);
+  return encode_impl(ctx, cfg, imgs, pack, norm, lfq, out, nullptr, nullptr, nullptr, (hipStream_t)stream, w_in_dev,
+                     b_in_dev);
+}
+
+int dctae_spectrum_tokens(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const int64_t* tok_off,
+                          float* tokens_dev, float* scores_dev, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (!tok_off || !scores_dev) return fail(ctx, DCTAE_EINVAL, "tok_off and scores_dev are required");
+  hipSetDevice(ctx->device);
+  return encode_impl(ctx, cfg, imgs, nullptr, nullptr, nullptr, nullptr, tok_off, tokens_dev, scores_dev,
+                     (hipStream_t)stream);
+}
+
+// Full-image orthonormal 2-D DCT (util.py:333-338 on the whole (3, H, W) image)
+// with the optional colour transform: FE._transform_image_in / _out
+// (FE:129-152) for callers that run (or override) the stages one by one.
+// Two MFMA GEMMs per image on the full DCT matrices (no kept-corner crop).
+int dctae_dct2(dctae_ctx* ctx, const float* x, int32_t n_img, int32_t H, int32_t W, int32_t direction, int32_t color,
+               float* y, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  if (n_img < 0 || H < 1 || W < 1 || (direction != 0 && direction != 1)) return fail(ctx, DCTAE_EINVAL, "bad dct2 shape");
+  if (color < 0 || color > 3 || (color > 1 && direction != 0))
+    return fail(ctx, DCTAE_EINVAL, "dct2 color: 0 none, 1 fp32, 2 / 3 fp16 / bf16 arithmetic (forward only)");
+  if (n_img == 0) return 0;
+  if (!x || !y || x == y) return fail(ctx, DCTAE_EINVAL, "dct2 needs distinct input / output buffers");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  const int64_t hw = (int64_t)H * W, plane = 3 * hw;
+  const float *CW, *CH;
+  if ((rc = dct_matrix(ctx, W, W, &CW)) || (rc = dct_matrix(ctx, H, H, &CH))) return rc;
+  // workspace: IPT (forward with colour) and the intermediate U / T, per image
+  if ((rc = ensure_ws(ctx, (size_t)2 * plane * n_img * 4, 256))) return rc;
+  float* a = ctx->ws;                        // forward: IPT input; inverse: IPT output
+  float* u = ctx->ws + plane * n_img;        // intermediate
+  std::vector<GemmProblem> probs;
+  std::vector<TileRef> t1, t2;
+  for (int i = 0; i < n_img; ++i) {
+    const int64_t o = plane * i;
+    GemmProblem g1, g2;
+    if (direction == 0) {
+      const float* src = color ? a + o : x + o;
+      // T[c][y][kx] = sum_x src[c][y][x] CW[kx][x];  Y[c][ky][kx] = sum_y CH[ky][y] T[c][y][kx]
+      g1 = gemm(src, hw, W, 1, CW, 0, W, 1, u + o, hw, W, 1, H, W, W, 3);
+      g2 = gemm(CH, 0, H, 1, u + o, hw, 1, W, y + o, hw, W, 1, H, W, H, 3);
+    } else {
+      float* dst = color ? a + o : y + o;
+      // U[c][y][kx] = sum_ky CH[ky][y] Y[c][ky][kx];  X[c][y][x] = sum_kx U[c][y][kx] CW[kx][x]
+      g1 = gemm(CH, 0, 1, H, x + o, hw, 1, W, u + o, hw, W, 1, H, W, H, 3);
+      g2 = gemm(u + o, hw, W, 1, CW, 0, 1, W, dst, hw, W, 1, H, W, W, 3);
+    }
+    attach_x3(ctx, g1);
+    attach_x3(ctx, g2);
+    const int pr = (int)probs.size();
+    probs.push_back(g1);
+    probs.push_back(g2);
+    add_tiles(t1, pr, g1);
+    add_tiles(t2, pr + 1, g2);
+  }
+  PlanBuf pb;
+  const size_t g_off = pb.add(probs.data(), probs.size());
+  const size_t t1_off = pb.add(t1.data(), t1.size());
+  const size_t t2_off = pb.add(t2.data(), t2.size());
+  order_after_previous(ctx, s);
+  if ((rc = upload_plan(ctx, pb, s))) return rc;
+  uint8_t* pd = ctx->plan_dev;
+  if (direction == 0 && color) {
+    Timer t(ctx, s, "rgb_to_ipt");
+    launch_color(x, a, hw, n_img, color >= 2 ? color : 0, ctx->cm, s);
+  }
+  {
+    Timer t(ctx, s, "dct2_gemm");
+    ctx_gemm(ctx, 3, (const GemmProblem*)(pd + g_off), (const TileRef*)(pd + t1_off), (int)t1.size(), s,
+                gemm_share(probs[0]));
+    ctx_gemm(ctx, 3, (const GemmProblem*)(pd + g_off), (const TileRef*)(pd + t2_off), (int)t2.size(), s,
+                gemm_share(probs[1]));
+  }
+  if (direction == 1 && color) {
+    Timer t(ctx, s, "ipt_to_rgb");
+    launch_color(a, y, hw, n_img, 1, ctx->cm, s);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+// FE._patch_image (FE:364-452) of one cropped spectrum (3, H, W), H and W
+// multiples of P: tiles of the kept corner, importance scores, (score desc,
+// index asc) order, top k -> patches (k, P*P), positions (k, 2), channels (k).
+int dctae_patch_spectrum(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const float* spec, int32_t H, int32_t W, int32_t k,
+                         float* patches, int64_t* positions, int64_t* channels, float* scores, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  int rc = check_cfg(ctx, cfg);
+  if (rc) return rc;
+  const int P = cfg->patch_size, PP = P * P;
+  if (H % P || W % P) return fail(ctx, DCTAE_EINVAL, "_patch_image: h and w must be multiples of patch_size (FE:368-369)");
+  ImgDesc d;
+  if ((rc = describe(ctx, cfg, H, W, d))) return rc;
+  if (k < 1 || k > d.T) return fail(ctx, DCTAE_EINVAL, "_patch_image: k out of range (FE:429-435)");
+  if (!spec || !patches || !positions || !channels) return fail(ctx, DCTAE_EINVAL, "NULL _patch_image buffer");
+  hipStream_t s = (hipStream_t)stream;
+  d.ws_y = 0;
+  d.tok_off = 0;
+  d.row = 0;
+  d.col = 0;
+  d.k = k;
+  d.local_id = 0;
+  const size_t y_bytes = (size_t)3 * d.Kh * d.Kw * 4;
+  const size_t st_scores = ((size_t)d.T * 4 + 255) & ~size_t(255), st_raw = (size_t)d.T * PP * 4;
+  const size_t st_ids = ((size_t)k * 8 + 255) & ~size_t(255);
+  if ((rc = ensure_ws(ctx, y_bytes, st_scores + st_raw + st_ids + 256))) return rc;
+  PlanBuf pb;
+  const size_t d_off = pb.add(&d, 1);
+  order_after_previous(ctx, s);
+  if ((rc = upload_plan(ctx, pb, s))) return rc;
+  const ImgDesc* dd = (const ImgDesc*)(ctx->plan_dev + d_off);
+  for (int c = 0; c < 3; ++c)   // kept corner (3, Kh, Kw) of the (3, H, W) spectrum
+    HIPCHK(ctx, hipMemcpy2DAsync(ctx->ws + (size_t)c * d.Kh * d.Kw, (size_t)d.Kw * 4, spec + (size_t)c * H * W,
+                                 (size_t)W * 4, (size_t)d.Kw * 4, d.Kh, hipMemcpyDeviceToDevice, s));
+  EncParams ep = enc_params(cfg, nullptr, nullptr);
+  ep.S = k;
+  TokenSinks sk{};
+  sk.scores = (float*)ctx->stage;
+  sk.raw = (float*)(ctx->stage + st_scores);
+  PackSinks ps{};
+  ps.pos = positions;
+  ps.ch = channels;
+  ps.ids = (int64_t*)(ctx->stage + st_scores + st_raw);
+  ps.raw = patches;
+  ps.scores = scores;
+  {
+    Timer t(ctx, s, "tile_epilogue");
+    launch_tile_epilogue(dd, 1, d.T, ctx->ws, ep, sk, s);
+  }
+  {
+    Timer t(ctx, s, "sort_pack");
+    launch_sort_pack(dd, 1, next_pow2(d.T), ep, sk, ps, s, ctx->opt.sort_kernel, d.T);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
+  return 0;
+}
+
+}  // extern "C"

@@ -13,7 +13,7 @@
 //   v[n] = x[2n], v[N-1-n] = x[2n+1];  z[m] = v[2m] + i v[2m+1];  Z = FFT_M(z)
 //   W_k = alpha_k (Z[k] + conj Z[M-k]) + beta_k (Z[k] - conj Z[M-k]),  k = 0..M
 //   X[k] = Re W_k,  X[N-k] = -Im W_k  (alpha/beta fold the twiddles and the
-//   ortho scale; tables built in float64 on the host, dctae_api.hip).
+//   ortho scale; tables built in float64 on the host, dctae_plan.hip).
 // Odd N (plan.odd): M = N, z[m] = v[m] + 0 i, X[k] = Re(w_k Z[k]) with
 //   w_k = s_k e^{-i pi k / (2N)} at post[2 k] (the same reordering; the
 //   real-FFT form of torch_dct.dct, util.py:333, for N without a factor 2).

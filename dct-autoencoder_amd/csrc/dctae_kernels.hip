@@ -1,5 +1,5 @@
 // HIP kernels (gfx950 / CDNA4) for the dct-autoencoder feature-extraction
-// hot path.  Host-side planning and the C ABI live in dctae_api.hip.
+// hot path.  Host-side planning and the C ABI live in the host units listed in dctae_ctx.h.
 //
 // Numerics notes (see DESIGN.md "Bit-exactness"):
 //  * compiled with -ffp-contract=off: every a*b+c below is two roundings

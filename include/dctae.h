@@ -456,7 +456,8 @@ int dctae_set_chunk_bytes(dctae_ctx* ctx, int64_t bytes);
  * also set by the environment variable DCTAE_WS_POISON=1 at context
  * creation; slow).  Profiling builds only (make PROFILING=1; the shipped
  * library returns DCTAE_EUNSUP): "bs_ablate", "t_alias", "gate" (these write
- * wrong outputs on purpose). */
+ * wrong outputs on purpose).  One table holds every key with its default and
+ * legal values: dct-autoencoder_amd/csrc/dctae_options.h. */
 int dctae_set_option(dctae_ctx* ctx, const char* key, int64_t value);
 
 /* Raise (return DCTAE_EINVAL) if a previous kernel of this context saw an

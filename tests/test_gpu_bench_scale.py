@@ -4,7 +4,7 @@ paths run that the small parity batches never select:
 * config 4 exactly as bench.py builds it (1024 ragged images, (H, W) ~
   U{14..1024}^2 from numpy default_rng(7), pixels from the counter RNG with
   seed 7): >= 64 GEMM problems, so the encode's row / column GEMM tiles and the
-  decode's GEMM tiles are dealt to XCDs per problem (dctae_api.hip
+  decode's GEMM tiles are dealt to XCDs per problem (dctae_plan.hip
   xcd_deal_tiles); sampled images against the oracle (FE:129-177, 364-452,
   patchnorm.py:157-165, lfq.py:136-187) and bit for bit against a small batch
   of the same images (the other dealing branch), and decoded images against

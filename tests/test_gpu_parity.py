@@ -879,7 +879,7 @@ def test_cols_wide_bit_identical(fe, pn, lfq):
         assert torch.equal(getattr(dp0, f), getattr(dp1, f)), f
 
 
-HALVES_DEFAULT = 0   # dctae_ctx::halves
+HALVES_DEFAULT = 0   # Options::halves (csrc/dctae_options.h)
 
 
 @pytest.mark.parametrize("n", [33, 64])

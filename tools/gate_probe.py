@@ -3,9 +3,9 @@ each other's latency when they run co-resident with T held in cache?
 
 Needs the profiling build (DCTAE_LIBRARY=_ab/libprof.so, `make PROFILING=1`):
 option t_alias=K makes images share K T' slots (T' stays in L2 / MALL, outputs
-WRONG), option gate=M launches part of the band path (dctae_api.hip
-dctae_ctx::gate).  For every (K, M) the 1024 x 512^2 BatchEncoder call is timed
-over --steps back-to-back calls with HIP events on its stream (the side stream
+WRONG), option gate=M launches part of the band path (Options::gate in
+dctae_options.h, run_gate in dctae_encode.hip).  For every (K, M) the
+1024 x 512^2 BatchEncoder call is timed over --steps back-to-back calls with HIP events on its stream (the side stream
 joins it inside the call).  One JSON line per case, then a summary line.
 Runs on the GPU box; reads nothing outside the repo."""
 import argparse
