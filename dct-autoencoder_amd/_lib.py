@@ -89,6 +89,12 @@ _SIGS = {
                            C.c_int),
     "dctae_norm_inverse": ([_P, C.POINTER(Norm), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P, _P],
                            C.c_int),
+    "dctae_norm_inverse_backward": ([_P, C.POINTER(Norm), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P,
+                                     _P], C.c_int),
+    "dctae_rec_loss_forward": ([_P, C.POINTER(Norm), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                C.c_int64, _P, _P, _P], C.c_int),
+    "dctae_rec_loss_backward": ([_P, C.POINTER(Norm), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                 C.c_int64, _P, _P, _P, _P, _P], C.c_int),
     "dctae_lfq_forward": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, _P, _P, _P], C.c_int),
     "dctae_lfq_indices_to_codes": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, _P, _P], C.c_int),
     "dctae_lfq_entropy_forward": ([_P, C.POINTER(LFQCfg), _P, _P, C.c_int64, C.c_float, C.c_float, _P, _P, _P],

@@ -258,6 +258,79 @@ def norm_train_step(x, channels, positions, key_pad, n, median, b, p: FEParams, 
     return y
 
 
+def _norm_tables(norm: NormState, p: FEParams, dev):
+    _check_dev(norm.median, norm.b)
+    tshape = (3, p.max_patch_h, p.max_patch_w, p.patch_size ** 2)
+    for t in (norm.median, norm.b):
+        if tuple(t.shape) != tshape or not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev:
+            raise AssertionError(f"PatchNorm tables must be contiguous fp32 {tshape} on {dev}, got {tuple(t.shape)}")
+
+
+def norm_inverse_backward(grad: torch.Tensor, channels: torch.Tensor, positions: torch.Tensor, norm: NormState,
+                          p: FEParams) -> torch.Tensor:
+    """grad * (b*sqrt(2) + eps) gathered per token (dctae_norm_inverse_backward):
+    the gradient of PatchNorm.inverse_norm with respect to its input, fp32."""
+    dev, gs, ch, pos, _, n = _stats_inputs(grad, channels, positions, None, p)
+    _norm_tables(norm, p, dev)
+    ctx = _lib.context(dev)
+    dy = torch.empty_like(gs)
+    rc = ctx.lib.dctae_norm_inverse_backward(ctx.h, C.byref(norm.c()), p.patch_size, p.max_patch_h, p.max_patch_w,
+                                             ptr(gs), ptr(ch), ptr(pos), n, ptr(dy), _lib.stream_ptr(dev))
+    ctx.check(rc, "dctae_norm_inverse_backward")
+    return dy
+
+
+def _rec_loss_inputs(out, tn, raw, channels, positions, key_pad, norm: NormState, p: FEParams):
+    if key_pad is None:
+        raise AssertionError("the reconstruction losses need the key_pad_mask")
+    dev, os_, ch, pos, kp, n = _stats_inputs(out.detach(), channels, positions, key_pad, p)
+    _check_dev(tn, raw)
+    _norm_tables(norm, p, dev)
+    ts, rs = tn.detach().float().contiguous(), raw.detach().float().contiguous()
+    if ts.shape != os_.shape or rs.shape != os_.shape:
+        raise AssertionError(f"targets {tuple(ts.shape)} / {tuple(rs.shape)} do not match the output {tuple(os_.shape)}")
+    return dev, os_, ts, rs, ch, pos, kp.view(torch.uint8), n
+
+
+def rec_loss_forward(out, tn, raw, channels, positions, key_pad, norm: NormState, p: FEParams, want_unnorm=True):
+    """The masked L1 pair of a training step (dctae_rec_loss_forward): scalars
+    (3) = [rec_loss, rec_loss_unnormalized, M] fp32 on the device, and
+    inverse_norm(out) at every token (None unless wanted).  key_pad: True at
+    padding."""
+    dev, os_, ts, rs, ch, pos, kp, n = _rec_loss_inputs(out, tn, raw, channels, positions, key_pad, norm, p)
+    ctx = _lib.context(dev)
+    sc = torch.empty(3, dtype=torch.float32, device=dev)
+    un = torch.empty_like(os_) if want_unnorm else None
+    rc = ctx.lib.dctae_rec_loss_forward(ctx.h, C.byref(norm.c()), p.patch_size, p.max_patch_h, p.max_patch_w, ptr(os_),
+                                        ptr(ts), ptr(rs), ptr(ch), ptr(pos), ptr(kp), n, ptr(un), ptr(sc),
+                                        _lib.stream_ptr(dev))
+    ctx.check(rc, "dctae_rec_loss_forward")
+    return sc, un
+
+
+def rec_loss_backward(out, tn, raw, channels, positions, key_pad, norm: NormState, p: FEParams, sc: torch.Tensor,
+                      grad: torch.Tensor, grad_unnorm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d(g0 rec_loss + g1 rec_loss_unnormalized + <grad_unnorm, unnorm>) / d out,
+    fp32, out's shape (dctae_rec_loss_backward).  sc: rec_loss_forward's
+    scalars for the same tensors; grad: the two upstream gradients, (2) on the
+    device."""
+    dev, os_, ts, rs, ch, pos, kp, n = _rec_loss_inputs(out, tn, raw, channels, positions, key_pad, norm, p)
+    _check_dev(sc, grad, grad_unnorm)
+    ctx = _lib.context(dev)
+    g = grad.detach().to(device=dev, dtype=torch.float32).reshape(2).contiguous()
+    gu = None
+    if grad_unnorm is not None:
+        gu = grad_unnorm.detach().float().contiguous()
+        if gu.shape != os_.shape:
+            raise AssertionError("the gradient of the unnormalized patches does not match the output")
+    dout = torch.empty_like(os_)
+    rc = ctx.lib.dctae_rec_loss_backward(ctx.h, C.byref(norm.c()), p.patch_size, p.max_patch_h, p.max_patch_w,
+                                         ptr(os_), ptr(ts), ptr(rs), ptr(ch), ptr(pos), ptr(kp), n, ptr(sc), ptr(g),
+                                         ptr(gu), ptr(dout), _lib.stream_ptr(dev))
+    ctx.check(rc, "dctae_rec_loss_backward")
+    return dout
+
+
 def check_device_errors(dev):
     ctx = _lib.context(dev)
     ctx.check(ctx.lib.dctae_check_device_errors(ctx.h, _lib.stream_ptr(dev)), "device index check")

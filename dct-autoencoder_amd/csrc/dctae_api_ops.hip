@@ -50,6 +50,65 @@ int dctae_norm_inverse(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_
   return norm_impl(ctx, norm, P, mh, mw, y, ch, pos, n, x, 1, stream);
 }
 
+// ---- reconstruction losses (main.py:71, 79-83) and inverse PatchNorm's gradient, dctae_rec_loss.hip ----
+static int rec_loss_check(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t mh, int32_t mw, int64_t n) {
+  if (!norm || !norm->median_dev || !norm->b_dev) return fail(ctx, DCTAE_EINVAL, "PatchNorm tables are NULL");
+  if (P < 1 || P > 1024 || mh < 1 || mw < 1 || n < 0) return fail(ctx, DCTAE_EINVAL, "bad PatchNorm shape");
+  if (!rec_loss_supported(n, P * P)) return fail(ctx, DCTAE_EUNSUP, "reconstruction losses: too many tokens in one call");
+  return 0;
+}
+
+int dctae_norm_inverse_backward(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t mh, int32_t mw,
+                                const float* grad, const int64_t* ch, const int64_t* pos, int64_t n, float* dy,
+                                void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  if (int rc = rec_loss_check(ctx, norm, P, mh, mw, n)) return rc;
+  if (n == 0) return 0;
+  if (!grad || !ch || !pos || !dy) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "norm_inverse_backward");
+  launch_rec_loss_bwd(nullptr, nullptr, nullptr, ch, pos, nullptr, n, P * P, mh, mw, norm->median_dev, norm->b_dev,
+                      norm->eps, nullptr, nullptr, grad, dy, ctx->err_dev, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_rec_loss_forward(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t mh, int32_t mw, const float* out,
+                           const float* tn, const float* raw, const int64_t* ch, const int64_t* pos,
+                           const uint8_t* key_pad, int64_t n, float* unnorm, float* scalars, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  if (int rc = rec_loss_check(ctx, norm, P, mh, mw, n)) return rc;
+  if (!scalars) return fail(ctx, DCTAE_EINVAL, "NULL output");
+  if (n > 0 && (!out || !tn || !raw || !ch || !pos || !key_pad)) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  if (int rc = ensure_ws(ctx, rec_loss_ws_bytes(n, P * P), 256)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "rec_loss_forward");
+  launch_rec_loss_fwd(out, tn, raw, ch, pos, key_pad, n, P * P, mh, mw, norm->median_dev, norm->b_dev, norm->eps,
+                      unnorm, ctx->ws, scalars, ctx->err_dev, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_rec_loss_backward(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t mh, int32_t mw,
+                            const float* out, const float* tn, const float* raw, const int64_t* ch, const int64_t* pos,
+                            const uint8_t* key_pad, int64_t n, const float* scalars, const float* grad,
+                            const float* grad_unnorm, float* dout, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  hipSetDevice(ctx->device);
+  if (int rc = rec_loss_check(ctx, norm, P, mh, mw, n)) return rc;
+  if (!scalars || !grad) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  if (n == 0) return 0;
+  if (!out || !tn || !raw || !ch || !pos || !key_pad || !dout) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "rec_loss_backward");
+  launch_rec_loss_bwd(out, tn, raw, ch, pos, key_pad, n, P * P, mh, mw, norm->median_dev, norm->b_dev, norm->eps,
+                      scalars, grad, grad_unnorm, dout, ctx->err_dev, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
 // ---- PatchNorm training (patchnorm.py:101-155), kernels in dctae_stats.hip ----
 namespace {
 

@@ -89,6 +89,19 @@ int launch_lfq_entropy_bwd(const float* h, const uint8_t* mask, int64_t n_tok, i
 bool linear_ordered_supported(int K, int D);
 void launch_linear_ordered(const float* x, int64_t n, int K, const float* wt, const float* b, int D, float* out,
                            hipStream_t st);
+// dctae_rec_loss.hip: the masked L1 reconstruction losses and their gradient, inverse PatchNorm's gradient
+bool rec_loss_supported(int64_t n_tok, int PP);
+size_t rec_loss_ws_bytes(int64_t n_tok, int PP);
+// scalars[0..2] = rec_loss, rec_loss_unnormalized, M; unnorm (nullable): inverse_norm(out) at every token
+void launch_rec_loss_fwd(const float* out, const float* tn, const float* raw, const int64_t* ch, const int64_t* pos,
+                         const uint8_t* key_pad, int64_t n_tok, int PP, int maxph, int maxpw, const float* med,
+                         const float* b, float eps, float* unnorm, void* ws, float* scalars, int* err,
+                         hipStream_t st);
+// g: the two losses' upstream gradients, gu (nullable): unnorm's; out == NULL: dout = gu std alone
+void launch_rec_loss_bwd(const float* out, const float* tn, const float* raw, const int64_t* ch, const int64_t* pos,
+                         const uint8_t* key_pad, int64_t n_tok, int PP, int maxph, int maxpw, const float* med,
+                         const float* b, float eps, const float* scalars, const float* g, const float* gu,
+                         float* dout, int* err, hipStream_t st);
 // VectorQuantize inference (dctae_vq.hip)
 void launch_vq_bias(float* y, const float* bias, int64_t n, int cols, const uint8_t* mask, const float* orig,
                     hipStream_t s);

@@ -18,6 +18,11 @@ Differences from the reference, both deliberate:
     ``mask.sum() == 0`` gives NaN, as in the reference.
   * non-fp32 features are upcast to fp32 before the kernel; the reference
     first rounds the dense distance to the model dtype.
+
+The other two terms of the reference's training step (main.py:44-93) are
+here as well: ``reconstruction_losses`` (the masked L1 pair on the normalized
+and the inverse-normalized output, fused HIP forward and backward on a GPU),
+``masked_perplexity`` and ``step_losses``, the dict of main.py:85-93.
 """
 from __future__ import annotations
 
@@ -159,6 +164,99 @@ def compute_entropy_loss(affinity, mask, temperature=0.01, eps=1e-9):
     avg_entropy = -(avg_probs * torch.log(avg_probs + eps)).sum()
     sample_entropy = -masked_mean((probs * log_probs).sum(dim=-1), m)
     return (sample_entropy - avg_entropy).to(og_dtype)
+
+
+class _FusedRecLoss(torch.autograd.Function):
+    """rec_loss, rec_loss_unnormalized and inverse_norm(out) from one pass
+    (dctae_rec_loss_forward); the backward recomputes the signs from the
+    inputs (dctae_rec_loss_backward), nothing is saved per element."""
+
+    @staticmethod
+    def forward(ctx, out, tn, raw, channels, positions, key_pad, state, params, want_unnorm):
+        sc, un = _ops.rec_loss_forward(out, tn, raw, channels, positions, key_pad, state, params, want_unnorm)
+        ctx.save_for_backward(out, tn, raw, channels, positions, key_pad, sc)
+        ctx.args = (state, params)
+        ctx.set_materialize_grads(False)
+        if un is not None:
+            un = un.view(out.shape)
+        return sc[0].clone(), sc[1].clone(), un
+
+    @staticmethod
+    def backward(ctx, g_rec, g_unn, g_patches):
+        out, tn, raw, channels, positions, key_pad, sc = ctx.saved_tensors
+        state, params = ctx.args
+        zero = torch.zeros((), dtype=torch.float32, device=out.device)
+        g = torch.stack([zero if t is None else t.float().reshape(()) for t in (g_rec, g_unn)])
+        dout = _ops.rec_loss_backward(out, tn, raw, channels, positions, key_pad, state, params, sc, g, g_patches)
+        return dout.view(out.shape).to(out.dtype), None, None, None, None, None, None, None, None
+
+
+def _inverse_norm_torch(patchnorm, dp, x):
+    """patchnorm.py:167-177 with torch ops, on x in place of dp.patches"""
+    c, h, w = dp.patch_channels, dp.h_indices, dp.w_indices
+    std = patchnorm.b[c, h, w] * 2 ** 0.5 + patchnorm.eps
+    return x * std + patchnorm.median[c, h, w]
+
+
+def reconstruction_losses(output, normalized_target, target, patchnorm, want_unnormalized=True):
+    """The reconstruction terms of the reference's step_autoencoder
+    (main.py:71, 79-83), arguments ``DCTPatches``, mask = ~output.key_pad_mask:
+
+        rec_loss = F.l1_loss(output.patches[mask], normalized_target.patches[mask])
+        rec_patches_unnormalized = patchnorm.inverse_norm(output)
+        rec_loss_unnormalized = F.l1_loss(rec_patches_unnormalized[mask], target.patches[mask])
+
+    Returns (rec_loss, rec_loss_unnormalized, rec_patches_unnormalized); the
+    last is None unless wanted.  All three carry gradients to
+    ``output.patches``.  On a GPU this is one autograd Function over the fused
+    HIP kernels (dctae_rec_loss_forward / _backward): no boolean index, so no
+    host synchronisation.  On CPU tensors the formula above runs with torch ops.
+
+    Differences from the reference, both deliberate (as for the entropy loss):
+      * the fused path never reads the targets of padded tokens, so a NaN there
+        does not reach the losses (the reference's index drops them too); a NaN
+        in a real token gives NaN and no real token at all gives NaN.
+      * fp16 / bf16 tensors are upcast to fp32 before the kernel, the losses and
+        rec_patches_unnormalized are fp32 and the gradient is cast back to the
+        output's dtype.  The reference gets the same promotion from its fp32
+        targets and tables; with half-precision targets it would compute in half."""
+    import torch.nn.functional as F
+    out = output.patches
+    if out.is_cuda:
+        return _FusedRecLoss.apply(out, normalized_target.patches, target.patches, output.patch_channels,
+                                   output.patch_positions, output.key_pad_mask, patchnorm.state(),
+                                   patchnorm._params(), bool(want_unnormalized))
+    mask = ~output.key_pad_mask
+    rec = F.l1_loss(out[mask], normalized_target.patches[mask])
+    un = _inverse_norm_torch(patchnorm, output, out)
+    rec_un = F.l1_loss(un[mask], target.patches[mask])
+    return rec, rec_un, (un if want_unnormalized else None)
+
+
+def masked_perplexity(codes, mask, codebook_size):
+    """``calculate_perplexity(codes[mask], codebook_size)`` (main.py:73-76)
+    without the boolean index: the codes of masked-out tokens become the null
+    index.  codes (b, s, ...) integer, mask (b, s): True at real tokens."""
+    m = mask.reshape(*mask.shape, *([1] * (codes.ndim - mask.ndim)))
+    return calculate_perplexity(torch.where(m, codes, torch.full_like(codes, -1)), codebook_size)
+
+
+def step_losses(res, batch, normalized_batch, patchnorm, codebook_size, training=True):
+    """The dict the reference's step_autoencoder returns (main.py:85-93, without
+    decode_pixels) from the model's output ``res`` (``dct_patches``, ``codes``,
+    ``commit_loss``, ``distances``), the raw ``batch`` and the
+    ``normalized_batch`` it was fed."""
+    output = res["dct_patches"]
+    mask = ~output.key_pad_mask
+    entropy_loss = compute_entropy_loss(res["distances"], mask) if training else 0.0
+    rec_loss, rec_loss_unnormalized, un = reconstruction_losses(output, normalized_batch, batch, patchnorm)
+    with torch.no_grad():
+        perplexity = masked_perplexity(res["codes"], mask, codebook_size)
+    unnormalized = output.shallow_copy()
+    unnormalized.patches = un
+    return dict(rec_patches=output, rec_patches_unnormalized=unnormalized, rec_loss=rec_loss,
+                rec_loss_unnormalized=rec_loss_unnormalized, perplexity=perplexity,
+                commit_loss=res["commit_loss"], entropy_loss=entropy_loss)
 
 
 def calculate_perplexity(codes, codebook_size, null_index=-1):

@@ -71,6 +71,28 @@ class PatchNorm(nn.Module):
                                self.state(), self._params(), inverse=False)
 
     def inverse_norm(self, dct_patches: DCTPatches) -> torch.Tensor:
-        """patchnorm.py:167-177"""
-        return _ops.norm_apply(dct_patches.patches, dct_patches.patch_channels, dct_patches.patch_positions,
+        """patchnorm.py:167-177.  Differentiable in the patches: an input that
+        requires grad gets the same values with a grad_fn whose backward is
+        grad * std (dctae_norm_inverse_backward); the tables get no gradient
+        (they are buffers).  The result is fp32, as without grad."""
+        x = dct_patches.patches
+        if x.requires_grad and torch.is_grad_enabled():
+            return _InverseNorm.apply(x, dct_patches.patch_channels, dct_patches.patch_positions, self.state(),
+                                      self._params())
+        return _ops.norm_apply(x, dct_patches.patch_channels, dct_patches.patch_positions,
                                self.state(), self._params(), inverse=True)
+
+
+class _InverseNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, channels, positions, state, params):
+        ctx.save_for_backward(channels, positions)
+        ctx.args = (state, params, x.dtype)
+        return _ops.norm_apply(x, channels, positions, state, params, inverse=True)
+
+    @staticmethod
+    def backward(ctx, grad):
+        channels, positions = ctx.saved_tensors
+        state, params, dtype = ctx.args
+        dx = _ops.norm_inverse_backward(grad, channels, positions, state, params)
+        return dx.view(grad.shape).to(dtype), None, None, None, None

@@ -170,6 +170,51 @@ int dctae_norm_inverse(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_
                        int32_t max_patch_w, const float* y_dev, const int64_t* channels_dev,
                        const int64_t* positions_dev, int64_t n, float* x_dev, void* stream);
 
+/* Gradient of PatchNorm.inverse_norm (patchnorm.py:167-177) with respect to
+ * its input: dy = grad * std, std = b*sqrt(2) + eps gathered per token as the
+ * forward forms it.  grad_dev / dy_dev: (n, P*P) fp32. */
+int dctae_norm_inverse_backward(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t max_patch_h,
+                                int32_t max_patch_w, const float* grad_dev, const int64_t* channels_dev,
+                                const int64_t* positions_dev, int64_t n, float* dy_dev, void* stream);
+
+/* The two reconstruction losses of a training step (main.py:71, 79-83) in one
+ * pass over n packed tokens of P*P fp32:
+ *   rec_loss              = F.l1_loss(out[mask], tn[mask])
+ *   rec_loss_unnormalized = F.l1_loss(inverse_norm(out)[mask], raw[mask])
+ * with mask = (key_pad == 0) and inverse_norm as dctae_norm_inverse
+ * (patchnorm.py:167-177), without the boolean index and its host
+ * synchronisation.  out_dev: the model's output, tn_dev: the normalized target,
+ * raw_dev: the raw target; key_pad_dev (n bytes): nonzero at padding.  tn / raw
+ * of padded tokens are never read (the reference drops them through the
+ * index; a NaN there leaves the losses alone).  unnorm_dev (nullable): receives
+ * inverse_norm(out) for every token, padding included (main.py:79); only then
+ * is out read at padded tokens.  scalars_dev: 3 floats = rec_loss,
+ * rec_loss_unnormalized, M (real tokens); each loss is its sum / (M * P*P), NaN
+ * for M = 0 as F.l1_loss of an empty selection.  A channel / position outside
+ * the tables on a real token (with unnorm_dev, on any token) makes the losses
+ * NaN and sets the context's index error (dctae_check_device_errors).
+ * Bit-identical from run to run: block partials in the workspace, added in a
+ * fixed order, no floating-point atomics. */
+int dctae_rec_loss_forward(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t max_patch_h,
+                           int32_t max_patch_w, const float* out_dev, const float* tn_dev, const float* raw_dev,
+                           const int64_t* channels_dev, const int64_t* positions_dev, const uint8_t* key_pad_dev,
+                           int64_t n, float* unnorm_dev, float* scalars_dev, void* stream);
+
+/* Gradient of those losses (and of unnorm) with respect to out, in place of
+ * autograd through main.py:71, 79-83 and patchnorm.py:167-177:
+ *   dout = g0 sign(d1) / (M P*P) + (gU + g1 sign(d2) / (M P*P)) std
+ * at real tokens, d1 = out - tn, d2 = inverse_norm(out) - raw, sign(0) = 0,
+ * std = b*sqrt(2) + eps; gU std at padded tokens (exact zeros without gU).
+ * scalars_dev: the forward's output for the same tensors; grad_dev: the two
+ * losses' upstream gradients (2 fp32 on the device; nothing synchronises);
+ * grad_unnorm_dev (nullable): the upstream gradient of unnorm, (n, P*P).  The
+ * signs are recomputed from the inputs; nothing is saved per element. */
+int dctae_rec_loss_backward(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, int32_t max_patch_h,
+                            int32_t max_patch_w, const float* out_dev, const float* tn_dev, const float* raw_dev,
+                            const int64_t* channels_dev, const int64_t* positions_dev, const uint8_t* key_pad_dev,
+                            int64_t n, const float* scalars_dev, const float* grad_dev,
+                            const float* grad_unnorm_dev, float* dout_dev, void* stream);
+
 /* PatchNorm training statistics of one packed batch of n_tok tokens
  * (patchnorm.py:101-130; replaces the reference's scatter_add_3d + per-cell
  * torch.median loop).  key_pad_dev (n_tok bytes, nullable) marks padding.
