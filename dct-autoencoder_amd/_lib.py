@@ -149,6 +149,17 @@ _SIGS = {
     "dctae_model_to_bf16": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, _P], C.c_int),
     "dctae_model_lfq": ([_P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P, C.c_int64, _P, _P, _P, C.c_int64, _P],
                         C.c_int),
+    "dctae_model_attention_lse": ([_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P],
+                                  C.c_int),
+    "dctae_model_attention_bwd": ([_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P,
+                                   C.c_int64, _P, _P, _P, _P], C.c_int),
+    "dctae_model_transpose_pack": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P], C.c_int),
+    "dctae_model_colsum": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, _P, _P], C.c_int),
+    "dctae_model_layernorm_bwd": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_float, _P, C.c_int64, _P,
+                                   C.c_int64, C.c_int32, _P, _P, _P], C.c_int),
+    "dctae_model_qgelu": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P], C.c_int),
+    "dctae_model_qgelu_bwd": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P], C.c_int),
+    "dctae_model_pos_grad": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P], C.c_int),
 }
 
 _lib = None

@@ -703,4 +703,135 @@ int dctae_model_lfq(dctae_ctx* ctx, int64_t M, int32_t ncb, int32_t cbd, float s
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// training: the forward's attention with its log-sum-exp, and the backward
+// operators (dctae_model_bwd.hip)
+// ---------------------------------------------------------------------------
+int dctae_model_attention_lse(dctae_ctx* ctx, int32_t R, int32_t S, int32_t heads, int32_t head_dim, const uint16_t* qkv,
+                              const int64_t* ids, const uint8_t* key_pad, uint16_t* out, int64_t ldo, float* lse,
+                              void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (head_dim != 64) return fail(ctx, DCTAE_EUNSUP, "model_attention_lse: head_dim must be 64");
+  if (R < 0 || S <= 0 || heads <= 0 || ldo < 64ll * heads || ldo % 8)
+    return fail(ctx, DCTAE_EINVAL, "model_attention_lse: bad shape");
+  if (R == 0) return 0;
+  if (!qkv || !ids || !key_pad || !out || !lse || !al16(qkv) || !al16(out))
+    return fail(ctx, DCTAE_EINVAL, "model_attention_lse: null or unaligned tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  AttnArgs a{qkv, ids, key_pad, out, R, S, heads, (int32_t)ldo, 0.125f, lse};
+  Timer t(ctx, s, "model_attention_lse");
+  launch_attention(a, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_attention_bwd(dctae_ctx* ctx, int32_t R, int32_t S, int32_t heads, int32_t head_dim, const uint16_t* qkv,
+                              const int64_t* ids, const uint8_t* key_pad, const uint16_t* out, int64_t ldo,
+                              const uint16_t* d_out, int64_t lddo, const float* lse, float* delta_ws, uint16_t* dqkv,
+                              void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (head_dim != 64) return fail(ctx, DCTAE_EUNSUP, "model_attention_bwd: head_dim must be 64");
+  if (R < 0 || S <= 0 || heads <= 0 || ldo < 64ll * heads || ldo % 8 || lddo < 64ll * heads || lddo % 8)
+    return fail(ctx, DCTAE_EINVAL, "model_attention_bwd: bad shape");
+  if (R == 0) return 0;
+  if (!qkv || !ids || !key_pad || !out || !d_out || !lse || !delta_ws || !dqkv || !al16(qkv) || !al16(out) ||
+      !al16(d_out) || !al16(dqkv))
+    return fail(ctx, DCTAE_EINVAL, "model_attention_bwd: null or unaligned tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  AttnBwdArgs a{qkv, out, d_out, lse, ids, key_pad, delta_ws, dqkv, R, S, heads, (int32_t)ldo, (int32_t)lddo, 0.125f};
+  Timer t(ctx, s, "model_attention_bwd");
+  launch_attention_bwd(a, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_transpose_pack(dctae_ctx* ctx, int64_t M, int32_t C, const uint16_t* x, int64_t ldx, int64_t Mp,
+                               uint16_t* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || C < 0 || ldx < C || Mp < M || Mp % 64) return fail(ctx, DCTAE_EINVAL, "model_transpose_pack: bad shape");
+  if (Mp == 0 || C == 0) return 0;
+  if (!x || !out) return fail(ctx, DCTAE_EINVAL, "model_transpose_pack: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "model_transpose_pack");
+  launch_transpose_pack(x, ldx, M, C, Mp, out, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_colsum(dctae_ctx* ctx, int64_t M, int32_t N, const void* x, int64_t ldx, int32_t is_bf16, float* ws,
+                       float* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || N < 0 || ldx < N) return fail(ctx, DCTAE_EINVAL, "model_colsum: bad shape");
+  if (N == 0) return 0;
+  if ((M > 0 && !x) || !out || (M > 256 && !ws)) return fail(ctx, DCTAE_EINVAL, "model_colsum: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "model_colsum");
+  launch_colsum(x, ldx, M, N, is_bf16 != 0, ws, out, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_layernorm_bwd(dctae_ctx* ctx, int64_t M, int32_t D, const float* x, int64_t ldx, const float* g,
+                              float eps, const float* dy, int64_t lddy, float* dx, int64_t lddx, int32_t accumulate,
+                              float* part_g, float* part_b, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || D <= 0 || D > 2048 || ldx < D || lddy < D || lddx < D)
+    return fail(ctx, DCTAE_EINVAL, "model_layernorm_bwd: bad shape (D <= 2048)");
+  if (M == 0) return 0;
+  if (!x || !g || !dy || !dx || !part_g || !part_b) return fail(ctx, DCTAE_EINVAL, "model_layernorm_bwd: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  LnBwdArgs a{x, g, dy, dx, part_g, part_b, M, ldx, lddy, lddx, D, accumulate, eps};
+  Timer t(ctx, s, "model_layernorm_bwd");
+  launch_layernorm_bwd(a, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_qgelu(dctae_ctx* ctx, int64_t M, int32_t N, const uint16_t* pre, int64_t ldp, uint16_t* out,
+                      int64_t ldo, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || N < 0 || ldp < N || ldo < N) return fail(ctx, DCTAE_EINVAL, "model_qgelu: bad shape");
+  if (M == 0 || N == 0) return 0;
+  if (!pre || !out) return fail(ctx, DCTAE_EINVAL, "model_qgelu: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "model_qgelu");
+  launch_qgelu(pre, ldp, M, N, out, ldo, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_qgelu_bwd(dctae_ctx* ctx, int64_t M, int32_t N, const uint16_t* df, int64_t lddf, const uint16_t* pre,
+                          int64_t ldp, uint16_t* dpre, int64_t lddp, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || N < 0 || lddf < N || ldp < N || lddp < N) return fail(ctx, DCTAE_EINVAL, "model_qgelu_bwd: bad shape");
+  if (M == 0 || N == 0) return 0;
+  if (!df || !pre || !dpre) return fail(ctx, DCTAE_EINVAL, "model_qgelu_bwd: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "model_qgelu_bwd");
+  launch_qgelu_bwd(df, lddf, pre, ldp, M, N, dpre, lddp, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_model_pos_grad(dctae_ctx* ctx, int64_t M, int32_t D, const float* g, int64_t ldg, const int64_t* idx,
+                         int64_t idx_stride, int32_t rows, float* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (M < 0 || D <= 0 || ldg < D || rows < 0 || idx_stride <= 0) return fail(ctx, DCTAE_EINVAL, "model_pos_grad: bad shape");
+  if (rows == 0) return 0;
+  if ((M > 0 && (!g || !idx)) || !out) return fail(ctx, DCTAE_EINVAL, "model_pos_grad: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "model_pos_grad");
+  launch_pos_grad(g, ldg, M, D, idx, idx_stride, rows, out, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
 }  // extern "C"

@@ -24,6 +24,7 @@ struct AttnArgs {
   uint16_t* out;           // (R * S, ldo) bf16, head h at columns 64 h
   int32_t R, S, heads, ldo;
   float scale;             // d_head ** -0.5
+  float* lse;              // (R, heads, S) f32 log-sum-exp in log2 units (training forward), or null
 };
 
 struct LnArgs {
@@ -62,6 +63,44 @@ struct LfqArgs {
   int32_t ncb, cbd;
   float scale;
 };
+
+// backward (dctae_model_bwd.hip)
+struct AttnBwdArgs {
+  const uint16_t* qkv;     // (R * S, 3 * heads * 64) bf16, the forward's operand
+  const uint16_t* out;     // (R * S, ldo) bf16, the forward's result
+  const uint16_t* dout;    // (R * S, lddo) bf16
+  const float* lse;        // (R, heads, S) from the training forward (log2 units)
+  const int64_t* ids;
+  const uint8_t* key_pad;
+  float* delta;            // (R, heads, S) scratch: rowsum(dO * O)
+  uint16_t* dqkv;          // (R * S, 3 * heads * 64) bf16: dq | dk | dv
+  int32_t R, S, heads, ldo, lddo;
+  float scale;
+};
+
+constexpr int LN_RPW = 8;   // rows per wave of k_ln_bwd: part_g / part_b have ceil(M / LN_RPW) rows
+
+struct LnBwdArgs {
+  const float* x;
+  const float* gamma;
+  const float* dy;
+  float* dx;
+  float* part_g;           // (ceil(M / LN_RPW), D) partial sums of dy * xhat
+  float* part_b;           // ... of dy
+  int64_t M, ldx, lddy, lddx;
+  int32_t D, accumulate;   // accumulate: dx += (the fp32 gradient stream)
+  float eps;
+};
+
+void launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s);
+void launch_transpose_pack(const uint16_t* x, int64_t ldx, int64_t M, int C, int64_t Mp, uint16_t* out, hipStream_t s);
+void launch_colsum(const void* x, int64_t ldx, int64_t M, int N, bool bf16, float* ws, float* out, hipStream_t s);
+void launch_layernorm_bwd(const LnBwdArgs& a, hipStream_t s);
+void launch_qgelu(const uint16_t* pre, int64_t ldp, int64_t M, int N, uint16_t* out, int64_t ldo, hipStream_t s);
+void launch_qgelu_bwd(const uint16_t* df, int64_t lddf, const uint16_t* pre, int64_t ldp, int64_t M, int N, uint16_t* dpre,
+                      int64_t lddp, hipStream_t s);
+void launch_pos_grad(const float* g, int64_t ldg, int64_t M, int D, const int64_t* idx, int64_t istride, int rows,
+                     float* out, hipStream_t s);
 
 void launch_linear(const LinearArgs& a, int epi, hipStream_t s);
 void launch_attention(const AttnArgs& a, hipStream_t s);

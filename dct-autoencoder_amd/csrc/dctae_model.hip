@@ -252,6 +252,9 @@ void launch_linear(const LinearArgs& a, int epi, hipStream_t s) {
 // column groups tile the 64 banks; at 72 they were 2-way)
 constexpr int AQ = 256, AK = 64, AD = 64, ASTR = 72, AVS = 96, ATH = 4 * AQ / 2;   // ATH threads: one wave per 32 queries
 
+// LSE: the training variant also writes each (row, head, query)'s log-sum-exp
+// in log2 units, mrun + log2(lsum), for the backward (dctae_model_bwd.hip)
+template <bool LSE>
 __global__ __launch_bounds__(ATH) void k_attention(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t Ks[AK * ASTR];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[AK * AVS];   // row-major; read transposed (ds_read_b64_tr_b16)
@@ -405,6 +408,7 @@ __global__ __launch_bounds__(ATH) void k_attention(AttnArgs a) {
     lsum = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
   }
   const float inv = 1.0f / lsum;
+  if (LSE && lane < 32 && ql < S) a.lse[((int64_t)b * a.heads + h) * S + ql] = mrun + __log2f(lsum);
   // O^T[d = 32 dt + 8 (v/4) + 4 (l/32) + v%4][query l%32] -> Os[query][d] -> coalesced rows
   const int qr = wave * 32 + (lane & 31);
 #pragma unroll
@@ -426,7 +430,9 @@ __global__ __launch_bounds__(ATH) void k_attention(AttnArgs a) {
 
 void launch_attention(const AttnArgs& a, hipStream_t s) {
   if (a.R <= 0 || a.S <= 0) return;
-  hipLaunchKernelGGL(k_attention, dim3((a.S + AQ - 1) / AQ, a.heads, a.R), dim3(ATH), 0, s, a);
+  const dim3 grid((a.S + AQ - 1) / AQ, a.heads, a.R);
+  if (a.lse) hipLaunchKernelGGL(k_attention<true>, grid, dim3(ATH), 0, s, a);
+  else hipLaunchKernelGGL(k_attention<false>, grid, dim3(ATH), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """DCTAutoencoder — drop-in for the reference's transformer autoencoder around
 the LFQ bottleneck (dct_autoencoder/modeling_dct_autoencoder.py, with the
-CLIPEncoder of transformers==4.35.2), inference on MI355X.
+CLIPEncoder of transformers==4.35.2), inference and training on MI355X
+(DESIGN.md §4b / §4e).
 
 Same constructor (a ``DCTAutoencoderConfig``), parameter names / state-dict
 keys (a reference checkpoint loads with ``load_state_dict``), and methods
@@ -22,11 +23,19 @@ id equals the key's and the key is padding, FE:580-584) and nothing is masked
 ``batched_image_ids`` / ``key_pad_mask``, which is how the feature extractor
 defines it.
 
-The transformer has no backward here (nor the VectorQuantize variant its
-codebook updates): ``encode`` / ``decode`` in training mode raise
-NotImplementedError.  The quantizer's training losses are on the MI355X path:
-``self.vq_model`` (LFQ) runs in ``.train()`` on its own, and ``entropy_loss``
-(modeling:196-200) takes the ``LFQDistance`` it returns.
+``.eval()``: ``encode`` / ``decode`` / ``decode_from_codes`` / ``forward`` run
+under ``no_grad``.  ``.train()``: the same methods run under autograd
+(model_train.py: one ``torch.autograd.Function`` per CLIP layer, one each for
+the patch embedding, the decoder position add and ``proj_out``), forward and
+backward on HIP kernels with bf16 operands, fp32 master weights, fp32 residual
+and gradient streams and no floating-point atomics, so a step repeats bit for
+bit.  ``encode`` then goes through the quantizer's training forward
+(``self.vq_model(h, mask=~key_pad_mask)``: straight-through output, codes,
+commit loss, ``LFQDistance``, as modeling:153), and ``forward``'s dict feeds
+``losses.step_losses`` unchanged.  Training refuses, with NotImplementedError
+and before the input is looked at, a model whose parameters are not on a HIP
+device or not fp32, and ``dropout`` / ``attention_dropout`` != 0.  The
+``vq_type='vq'`` variant (VectorQuantize and its codebook updates) is not here.
 """
 from __future__ import annotations
 
@@ -38,6 +47,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from . import model_train as _train
 from .dct_patches import DCTPatches
 from .lfq import LFQ
 from .losses import compute_entropy_loss
@@ -147,6 +157,9 @@ class _Packed:
     def __init__(self, model: "DCTAutoencoder"):
         self.w: Dict[str, torch.Tensor] = {}
         self.b: Dict[str, Optional[torch.Tensor]] = {}
+        # training: (K, pad64(N)) transposed packs, the "weight" of dX = dY W on the same GEMM
+        self.wt: Dict[str, torch.Tensor] = {}
+        self.training = model.training
         for side in ("encoder", "decoder"):
             for i, L in enumerate(getattr(model, side).layers):
                 a = L.self_attn
@@ -164,6 +177,8 @@ class _Packed:
 
     def _put(self, name, w, b):
         self.w[name] = _bf16_padded(w, _pad64(w.shape[1]))
+        if self.training:
+            self.wt[name] = _bf16_padded(w.t(), _pad64(w.shape[0]))
         self.b[name] = b.detach().float().contiguous() if b is not None else None
 
 
@@ -244,15 +259,28 @@ class DCTAutoencoder(nn.Module):
 
     def _weights(self) -> _Packed:
         key = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._packed is None or self._packed_key != key:
+        if self._packed is None or self._packed_key != key or (self.training and not self._packed.training):
             self._packed = _Packed(self)
             self._packed_key = key
         return self._packed
 
+    def _check_train(self):
+        """Training-mode refusals, before the input is looked at."""
+        for n, p in self.named_parameters():
+            if p.device.type != "cuda":
+                raise NotImplementedError(f"DCTAutoencoder training runs on HIP kernels: parameter {n} is on "
+                                          f"{p.device} (move the model to the GPU, or call .eval())")
+            if p.dtype != torch.float32:
+                raise NotImplementedError(f"DCTAutoencoder training keeps fp32 master weights (bf16 operands are "
+                                          f"packed from them): parameter {n} is {p.dtype}")
+        for side in ("encoder_config", "decoder_config"):
+            c = getattr(self.config, side)
+            if c.dropout != 0 or c.attention_dropout != 0:
+                raise NotImplementedError(f"{side}: dropout / attention_dropout != 0 has no kernel in training")
+
     def _check_mode(self, dp: Optional[DCTPatches] = None):
         if self.training:
-            raise NotImplementedError("DCTAutoencoder training (losses, backward) is not on the MI355X path: "
-                                      "call .eval()")
+            self._check_train()
         if dp is not None:
             dev = dp.patches.device
             # kernels take raw device pointers: a parameter left on another device (or the
@@ -275,14 +303,14 @@ class DCTAutoencoder(nn.Module):
                 for k in ("height", "width", "channel")]
 
     @staticmethod
-    def _meta(dp: DCTPatches):
+    def _ch_pos(dp: DCTPatches):
         return (dp.patch_channels.reshape(-1).long().contiguous(),
                 dp.patch_positions.reshape(-1, 2).long().contiguous())
 
     def _pos_add(self, x, side, dp):
         ctx = self._ctx(x)
         d = x.shape[-1]
-        ch, pos = self._meta(dp)
+        ch, pos = self._ch_pos(dp)
         tabs = self._pos_tables(side)
         ctx.check(ctx.lib.dctae_model_pos_add(ctx.h, x.numel() // d, d, _lib.ptr(x), d, *[_lib.ptr(t) for t in tabs],
                                               _lib.ptr(ch), _lib.ptr(pos), _lib.stream_ptr(x.device)), "model_pos_add")
@@ -334,8 +362,41 @@ class DCTAutoencoder(nn.Module):
         return out
 
     # ---- modeling:119-200 ----
-    @torch.no_grad()
     def encode(self, dct_patches: DCTPatches, do_normalize: bool = False):
+        """modeling:119-147.  ``.eval()``: no_grad, LFQ codes only.  ``.train()``:
+        under autograd, through the quantizer's training forward (straight-through
+        output, codes, commit loss, ``LFQDistance``), as modeling:153."""
+        if self.training:
+            self._check_mode()
+            return self._encode_train(dct_patches, do_normalize)
+        return self._encode_eval(dct_patches, do_normalize)
+
+    def _meta(self, dp: DCTPatches, side: str):
+        tabs = [getattr(self, f"{side}_pos_embed_{k}") for k in ("height", "width", "channel")]
+        return _train.Meta(self._weights(), dp, getattr(self.config, f"{side}_config").num_attention_heads, tabs), tabs
+
+    def _encode_train(self, dct_patches: DCTPatches, do_normalize: bool):
+        if do_normalize:
+            dct_patches = self.normalize_(dct_patches)
+        r, s, d = *dct_patches.key_pad_mask.shape, self.config.encoder_config.hidden_size
+        h = self._encode_hidden(dct_patches)
+        xq, codes, commit_loss, distances = self.vq_model(h.view(r, s, d), mask=~dct_patches.key_pad_mask)
+        dct_patches.patches = xq
+        return dct_patches, codes, commit_loss, distances
+
+    def _encode_hidden(self, dct_patches: DCTPatches) -> torch.Tensor:
+        """The encoder's hidden state (R * S, D) before the quantizer, under autograd."""
+        self._check_mode(dct_patches)
+        meta, tabs = self._meta(dct_patches, "encoder")
+        x = dct_patches.patches
+        r, s, pd = x.shape
+        ln = self.to_patch_embedding[1]
+        h = _train.EmbedFn.apply(x.reshape(r * s, pd).float().contiguous(), meta, ln.eps,
+                                 self.to_patch_embedding[0].weight, ln.weight, ln.bias, *tabs)
+        return _train.clip_stack(self.encoder, "encoder", h, meta)
+
+    @torch.no_grad()
+    def _encode_eval(self, dct_patches: DCTPatches, do_normalize: bool = False):
         self._check_mode(dct_patches)
         if do_normalize:
             dct_patches = self.normalize_(dct_patches)
@@ -349,7 +410,7 @@ class DCTAutoencoder(nn.Module):
         e = self._linear(ctx, xb, pk.w["embed"], None, d, LIN_F32, torch.empty(r * s, d, device=dev))
         h = torch.empty(r * s, d, device=dev)
         ln = self.to_patch_embedding[1]
-        ch, pos = self._meta(dct_patches)
+        ch, pos = self._ch_pos(dct_patches)
         tabs = self._pos_tables("encoder")
         g, b = _f32(ln.weight), _f32(ln.bias)
         ctx.check(ctx.lib.dctae_model_embed_norm(ctx.h, r * s, d, _lib.ptr(e), d, _lib.ptr(g),
@@ -388,9 +449,18 @@ class DCTAutoencoder(nn.Module):
                                               _lib.ptr(codes), None, _lib.ptr(xq), d, st), "lfq")
         return xq, codes
 
-    @torch.no_grad()
     def decode_from_codes(self, codes: torch.LongTensor, do_inv_norm: bool = False, **dct_patches_kwargs) -> DCTPatches:
-        """modeling:149-158: LFQ.indices_to_codes (HIP kernel) + project_out (bf16 MFMA linear)."""
+        """modeling:149-158: LFQ.indices_to_codes (HIP kernel) + project_out (bf16
+        MFMA linear; in ``.train()`` the quantizer's differentiable project_out)."""
+        if self.training:
+            self._check_mode()
+            vq = self.vq_model
+            q = vq._project_out_train(vq.indices_to_codes(codes, project_out=False).float())
+            return self.decode(DCTPatches(patches=q, **dct_patches_kwargs), do_inv_norm=do_inv_norm)
+        return self._decode_from_codes_eval(codes, do_inv_norm, **dct_patches_kwargs)
+
+    @torch.no_grad()
+    def _decode_from_codes_eval(self, codes, do_inv_norm=False, **dct_patches_kwargs) -> DCTPatches:
         vq = self.vq_model
         q = vq.indices_to_codes(codes, project_out=False)
         if vq.has_projections:
@@ -404,8 +474,27 @@ class DCTAutoencoder(nn.Module):
         x = DCTPatches(patches=q, **dct_patches_kwargs)
         return self.decode(x, do_inv_norm=do_inv_norm)
 
-    @torch.no_grad()
     def decode(self, x: DCTPatches, do_inv_norm: bool = False) -> DCTPatches:
+        if self.training:
+            self._check_mode()
+            return self._decode_train(x, do_inv_norm)
+        return self._decode_eval(x, do_inv_norm)
+
+    def _decode_train(self, x: DCTPatches, do_inv_norm: bool) -> DCTPatches:
+        self._check_mode(x)
+        meta, tabs = self._meta(x, "decoder")
+        r, s, d = x.patches.shape
+        h = _train.PosAddFn.apply(x.patches.reshape(r * s, d).float().contiguous(), meta, *tabs)
+        h = _train.clip_stack(self.decoder, "decoder", h, meta)
+        ln, lin = self.proj_out
+        y = _train.ProjOutFn.apply(h, meta, ln.eps, ln.weight, ln.bias, lin.weight)
+        x.patches = y.view(r, s, -1)
+        if do_inv_norm:
+            x = self.inv_normalize_(x)
+        return x
+
+    @torch.no_grad()
+    def _decode_eval(self, x: DCTPatches, do_inv_norm: bool = False) -> DCTPatches:
         self._check_mode(x)
         pk = self._weights()
         r, s, d = x.patches.shape
@@ -422,8 +511,8 @@ class DCTAutoencoder(nn.Module):
             x = self.inv_normalize_(x)
         return x
 
-    @torch.no_grad()
     def forward(self, dct_patches: DCTPatches, do_normalize: bool = False):
+        """modeling:160-194; the dict feeds ``losses.step_losses`` unchanged."""
         dct_patches, codes, commit_loss, distances = self.encode(dct_patches, do_normalize=do_normalize)
         dct_patches = self.decode(dct_patches)
         return dict(dct_patches=dct_patches, commit_loss=commit_loss, codes=codes, distances=distances)

@@ -587,6 +587,56 @@ int dctae_model_lfq(dctae_ctx* ctx, int64_t M, int32_t ncb, int32_t cbd, float s
                     int64_t ldx, int64_t* codes_dev, uint16_t* q_bf16_dev, float* q_f32_dev, int64_t ldq,
                     void* stream);
 
+/* ---- transformer training step (additive; ABI version unchanged) ----
+ * bf16 operands, fp32 accumulation, no floating-point atomics: every result
+ * below repeats bit for bit. */
+
+/* dctae_model_attention that also writes lse (R, heads, S) f32: each query's
+ * log-sum-exp of its biased, scaled logits in log2 units. */
+int dctae_model_attention_lse(dctae_ctx* ctx, int32_t R, int32_t S, int32_t heads, int32_t head_dim,
+                              const uint16_t* qkv_dev, const int64_t* ids_dev, const uint8_t* key_pad_dev,
+                              uint16_t* out_dev, int64_t ldo, float* lse_dev, void* stream);
+
+/* Attention backward: dqkv (R*S, 3*heads*64) bf16 laid out like qkv from the
+ * forward's qkv, lse and d_out (R*S, lddo) bf16.  The +1.0 bias enters P and
+ * has no gradient.  delta_ws: (R, heads, S) f32 scratch for delta = sum_j P dP,
+ * taken from the recomputed P in fp32 (so every query's dS sums to zero); out,
+ * which gives the same delta as rowsum(d_out * out) only up to its bf16
+ * rounding, is checked but not read. */
+int dctae_model_attention_bwd(dctae_ctx* ctx, int32_t R, int32_t S, int32_t heads, int32_t head_dim,
+                              const uint16_t* qkv_dev, const int64_t* ids_dev, const uint8_t* key_pad_dev,
+                              const uint16_t* out_dev, int64_t ldo, const uint16_t* d_out_dev, int64_t lddo,
+                              const float* lse_dev, float* delta_ws_dev, uint16_t* dqkv_dev, void* stream);
+
+/* bf16 (M, C) -> (C, Mp), Mp % 64 == 0, columns M .. Mp zero: the operands of
+ * dW = dY^T X for dctae_model_linear (x = dY^T, w = X^T, K = Mp). */
+int dctae_model_transpose_pack(dctae_ctx* ctx, int64_t M, int32_t C, const uint16_t* x_dev, int64_t ldx, int64_t Mp,
+                               uint16_t* out_dev, void* stream);
+
+/* out (N) f32 = column sums of x (M, ldx) f32 or bf16 in a fixed order
+ * (bias gradients).  ws: ceil(M / 64) * N floats, needed when M > 256. */
+int dctae_model_colsum(dctae_ctx* ctx, int64_t M, int32_t N, const void* x_dev, int64_t ldx, int32_t is_bf16,
+                       float* ws_dev, float* out_dev, void* stream);
+
+/* LayerNorm backward from (x, gamma, dy), statistics recomputed: dx (added to
+ * dx_dev when accumulate != 0), and per-wave partial sums part_g / part_b
+ * (ceil(M / 8), D) of dy * xhat and dy; dctae_model_colsum of those gives
+ * dgamma and dbeta. */
+int dctae_model_layernorm_bwd(dctae_ctx* ctx, int64_t M, int32_t D, const float* x_dev, int64_t ldx,
+                              const float* gamma_dev, float eps, const float* dy_dev, int64_t lddy, float* dx_dev,
+                              int64_t lddx, int32_t accumulate, float* part_g_dev, float* part_b_dev, void* stream);
+
+/* quick_gelu of a bf16 pre-activation, and dpre = df * quick_gelu'(pre), bf16. */
+int dctae_model_qgelu(dctae_ctx* ctx, int64_t M, int32_t N, const uint16_t* pre_dev, int64_t ldp, uint16_t* out_dev,
+                      int64_t ldo, void* stream);
+int dctae_model_qgelu_bwd(dctae_ctx* ctx, int64_t M, int32_t N, const uint16_t* df_dev, int64_t lddf,
+                          const uint16_t* pre_dev, int64_t ldp, uint16_t* dpre_dev, int64_t lddp, void* stream);
+
+/* Position-table gradient: out (rows, D) f32, out[r] = sum of g[m] over the
+ * tokens with idx[m * idx_stride] == r, in token order. */
+int dctae_model_pos_grad(dctae_ctx* ctx, int64_t M, int32_t D, const float* g_dev, int64_t ldg, const int64_t* idx_dev,
+                         int64_t idx_stride, int32_t rows, float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
