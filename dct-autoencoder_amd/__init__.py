@@ -12,13 +12,14 @@ from .lfq import LFQ  # noqa: F401
 from .losses import (LFQDistance, calculate_perplexity, compute_entropy_loss, masked_mean,  # noqa: F401
                      masked_perplexity, reconstruction_losses, step_losses)
 from .model import CLIPEncoderConfig, DCTAutoencoder, DCTAutoencoderConfig  # noqa: F401
+from .optim import FusedAdamW  # noqa: F401
 from .patchnorm import PatchNorm  # noqa: F401
 from .vector_quantize import VectorQuantize  # noqa: F401
 from . import packing  # noqa: F401
 from . import shards  # noqa: F401
 
 __all__ = ["DCTAutoencoderFeatureExtractor", "DCTPatches", "PatchNorm", "LFQ", "VectorQuantize", "to_dict", "from_dict",
-           "DCTAutoencoder", "DCTAutoencoderConfig", "CLIPEncoderConfig",
+           "DCTAutoencoder", "DCTAutoencoderConfig", "CLIPEncoderConfig", "FusedAdamW",
            "GroupPatchesState", "build_attn_mask", "load_library", "DCTAEError", "DCTAEUnavailable",
            "LFQDistance", "compute_entropy_loss", "masked_mean", "calculate_perplexity",
            "reconstruction_losses", "masked_perplexity", "step_losses"]

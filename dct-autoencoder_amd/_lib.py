@@ -69,6 +69,20 @@ class VQCfg(C.Structure):
                 ("batch_variance_dev", C.c_void_p), ("batch_initted_dev", C.c_void_p)]
 
 
+class OptimSeg(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("w_dst", C.c_void_p), ("wt_dst", C.c_void_p), ("copy_dst", C.c_void_p),
+                ("rows", C.c_int64), ("cols", C.c_int64), ("ldw", C.c_int64), ("ldwt", C.c_int64),
+                ("w_row_off", C.c_int64), ("wt_col_off", C.c_int64), ("norm0", C.c_int64), ("work0", C.c_int64),
+                ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimGroup(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("decay", "w1", "beta2", "w2", "step_size", "bc2_sqrt", "eps", "reserved")]
+
+
+OPTIM_MAX_GROUPS = 16
+
 _P = C.c_void_p
 _SIGS = {
     "dctae_abi_version": ([], C.c_int),
@@ -160,6 +174,10 @@ _SIGS = {
     "dctae_model_qgelu": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P], C.c_int),
     "dctae_model_qgelu_bwd": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P], C.c_int),
     "dctae_model_pos_grad": ([_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P], C.c_int),
+    # fused optimizer step; the table is an OptimSeg array
+    "dctae_optim_plan": ([_P, _P, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+    "dctae_optim_gradnorm": ([_P, _P, C.c_int32, C.c_int64, C.c_float, _P, _P, _P], C.c_int),
+    "dctae_optim_adamw_pack": ([_P, _P, C.c_int32, C.c_int64, C.POINTER(OptimGroup), C.c_int32, _P, _P], C.c_int),
 }
 
 _lib = None

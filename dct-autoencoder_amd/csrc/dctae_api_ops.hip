@@ -1,6 +1,6 @@
 // C ABI entry points of the single operators: PatchNorm and its statistics,
-// LFQ (entropy and projections included), VectorQuantize and the transformer
-// operators of dctae_model.hip.
+// LFQ (entropy and projections included), VectorQuantize, the transformer
+// operators of dctae_model.hip and the fused optimizer step of dctae_optim.hip.
 #include "dctae_ctx.h"
 #include "dctae_model.h"
 
@@ -830,6 +830,68 @@ int dctae_model_pos_grad(dctae_ctx* ctx, int64_t M, int32_t D, const float* g, i
   hipStream_t s = (hipStream_t)stream;
   Timer t(ctx, s, "model_pos_grad");
   launch_pos_grad(g, ldg, M, D, idx, idx_stride, rows, out, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// fused optimizer step (dctae_optim.hip)
+// ---------------------------------------------------------------------------
+static int optim_fail(dctae_ctx* ctx, int code, const char* msg) { return ctx ? fail(ctx, code, msg) : code; }
+
+int dctae_optim_plan(dctae_ctx* ctx, dctae_optim_seg* segs, int32_t count, int64_t* n_norm_blocks, int64_t* n_work) {
+  if (count < 0 || (count > 0 && !segs) || !n_norm_blocks || !n_work)
+    return optim_fail(ctx, DCTAE_EINVAL, "optim_plan: bad arguments");
+  int64_t nb = 0, nw = 0;
+  for (int32_t i = 0; i < count; ++i) {
+    dctae_optim_seg& s = segs[i];
+    if (s.rows < 0 || s.cols < 0 || (s.cols > 0 && s.rows > INT64_MAX / s.cols))
+      return optim_fail(ctx, DCTAE_EINVAL, "optim_plan: bad segment shape");
+    const int64_t n = s.rows * s.cols;
+    if (n > 0 && (!s.p || !s.exp_avg || !s.exp_avg_sq)) return optim_fail(ctx, DCTAE_EINVAL, "optim_plan: null tensor");
+    if (s.group < 0 || s.group >= DCTAE_OPTIM_MAX_GROUPS) return optim_fail(ctx, DCTAE_EINVAL, "optim_plan: bad group");
+    const bool packed = s.w_dst || s.wt_dst;
+    if (packed && s.copy_dst) return optim_fail(ctx, DCTAE_EINVAL, "optim_plan: copy_dst on a packed segment");
+    if ((s.w_dst && (s.ldw < s.cols || s.w_row_off < 0)) || (s.wt_dst && (s.wt_col_off < 0 || s.ldwt < s.wt_col_off + s.rows)))
+      return optim_fail(ctx, DCTAE_EINVAL, "optim_plan: pack destination smaller than the segment");
+    s.norm0 = nb;
+    s.work0 = nw;
+    nb += (n + OPT_NORM_CHUNK - 1) / OPT_NORM_CHUNK;
+    nw += packed ? ((s.rows + OPT_TILE - 1) / OPT_TILE) * ((s.cols + OPT_TILE - 1) / OPT_TILE)
+                 : (n + OPT_FLAT_CHUNK - 1) / OPT_FLAT_CHUNK;
+  }
+  if (nb > INT32_MAX) return optim_fail(ctx, DCTAE_EUNSUP, "optim_plan: too many gradient elements for one launch");
+  *n_norm_blocks = nb;
+  *n_work = nw;
+  return 0;
+}
+
+int dctae_optim_gradnorm(dctae_ctx* ctx, const dctae_optim_seg* segs, int32_t count, int64_t n_norm_blocks,
+                         float max_norm, double* ws, float* stats, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (count < 0 || n_norm_blocks < 0 || n_norm_blocks > INT32_MAX) return fail(ctx, DCTAE_EINVAL, "optim_gradnorm: bad size");
+  if (!stats || (n_norm_blocks > 0 && (!segs || !ws || count == 0)))
+    return fail(ctx, DCTAE_EINVAL, "optim_gradnorm: null tensor");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "optim_gradnorm");
+  launch_gradnorm(segs, count, n_norm_blocks, max_norm, ws, stats, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_optim_adamw_pack(dctae_ctx* ctx, const dctae_optim_seg* segs, int32_t count, int64_t n_work,
+                           const dctae_optim_group* groups, int32_t n_groups, const float* stats, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (count < 0 || n_work < 0) return fail(ctx, DCTAE_EINVAL, "optim_adamw_pack: bad size");
+  if (n_groups < 1 || n_groups > DCTAE_OPTIM_MAX_GROUPS || !groups)
+    return fail(ctx, DCTAE_EUNSUP, "optim_adamw_pack: 1 .. DCTAE_OPTIM_MAX_GROUPS hyper-parameter groups");
+  if (n_work == 0) return 0;
+  if (!segs || count == 0) return fail(ctx, DCTAE_EINVAL, "optim_adamw_pack: null table");
+  hipSetDevice(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  Timer t(ctx, s, "optim_adamw_pack");
+  launch_adamw_pack(segs, count, n_work, groups, n_groups, stats, s);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/dctae.h"
+
 namespace dctae {
 
 enum { LIN_F32 = 0, LIN_BF16 = 1, LIN_BF16_QGELU = 2, LIN_F32_RESIDUAL = 3 };
@@ -101,6 +103,15 @@ void launch_qgelu_bwd(const uint16_t* df, int64_t lddf, const uint16_t* pre, int
                       int64_t lddp, hipStream_t s);
 void launch_pos_grad(const float* g, int64_t ldg, int64_t M, int D, const int64_t* idx, int64_t istride, int rows,
                      float* out, hipStream_t s);
+
+// fused optimizer step (dctae_optim.hip); the table is dctae_optim_seg of include/dctae.h
+constexpr int64_t OPT_NORM_CHUNK = 16384;   // gradient elements per block of k_gradnorm_partial
+constexpr int64_t OPT_FLAT_CHUNK = 4096;    // elements per flat work item of k_adamw_pack
+constexpr int OPT_TILE = 64;                // packed work item: OPT_TILE x OPT_TILE elements
+void launch_gradnorm(const dctae_optim_seg* segs, int count, int64_t n_blocks, float max_norm, double* ws, float* stats,
+                     hipStream_t s);
+void launch_adamw_pack(const dctae_optim_seg* segs, int count, int64_t n_work, const dctae_optim_group* groups,
+                       int n_groups, const float* stats, hipStream_t s);
 
 void launch_linear(const LinearArgs& a, int epi, hipStream_t s);
 void launch_attention(const AttnArgs& a, hipStream_t s);

@@ -40,6 +40,7 @@ device or not fp32, and ``dropout`` / ``attention_dropout`` != 0.  The
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -151,15 +152,72 @@ def _bf16_padded(w: torch.Tensor, kp: int) -> torch.Tensor:
     return out.view(torch.int16)
 
 
+_pack_generation = itertools.count(1)
+
+
+class _TrackedParameter(nn.Parameter):
+    """The nn.Parameter of a Linear that ``_Packed`` copies, counting accesses of ``.data``.
+    torch gives ``p.data`` a version counter of its own, so ``p.data.copy_(...)`` moves
+    neither ``p._version`` nor ``p.data_ptr()``; the count is the third part of
+    ``_param_stamp``, so the packed bf16 copies are rebuilt after any access that may have
+    been such a write (a read costs one rebuild, never a stale pack).  A tensor obtained from
+    ``.data`` earlier and written later is not seen.  Pickling gives back a plain Parameter."""
+    _data_reads = 0
+
+    @property
+    def data(self):
+        self._data_reads += 1
+        return torch.Tensor.data.__get__(self)
+
+    @data.setter
+    def data(self, value):
+        self._data_reads += 1
+        torch.Tensor.data.__set__(self, value)
+
+    def __deepcopy__(self, memo):   # nn.Parameter's, without going through .data
+        if id(self) in memo:
+            return memo[id(self)]
+        result = type(self)(self.detach().clone(memory_format=torch.preserve_format), self.requires_grad)
+        memo[id(self)] = result
+        return result
+
+    def __repr__(self):
+        return "Parameter containing:\n" + repr(self.detach().as_subclass(torch.Tensor))
+
+
+def _param_stamp(p):
+    """What identifies a parameter's current value to the pack caches."""
+    return p.data_ptr(), p._version, getattr(p, "_data_reads", 0)
+
+
+def _packed_linears(model: "DCTAutoencoder"):
+    """(name in _Packed, the nn.Linear modules stacked in that pack), as _Packed lays them out."""
+    for side in ("encoder", "decoder"):
+        for i, L in enumerate(getattr(model, side).layers):
+            a = L.self_attn
+            yield f"{side}.{i}.qkv", [a.q_proj, a.k_proj, a.v_proj]
+            yield f"{side}.{i}.out", [a.out_proj]
+            yield f"{side}.{i}.fc1", [L.mlp.fc1]
+            yield f"{side}.{i}.fc2", [L.mlp.fc2]
+    yield "embed", [model.to_patch_embedding[0]]
+    if model.vq_model.has_projections:
+        yield "proj_in", [model.vq_model.project_in]
+        yield "proj_out_vq", [model.vq_model.project_out]
+    yield "proj_out", [model.proj_out[1]]
+
+
 class _Packed:
     """bf16 device copies of the linear weights, built once per parameter version."""
 
-    def __init__(self, model: "DCTAutoencoder"):
+    def __init__(self, model: "DCTAutoencoder", training: Optional[bool] = None):
         self.w: Dict[str, torch.Tensor] = {}
         self.b: Dict[str, Optional[torch.Tensor]] = {}
         # training: (K, pad64(N)) transposed packs, the "weight" of dX = dY W on the same GEMM
         self.wt: Dict[str, torch.Tensor] = {}
-        self.training = model.training
+        self.training = model.training if training is None else training
+        # what a forward's Meta records and its backward checks: optim.FusedAdamW rewrites its
+        # pack in place and moves it to a new generation (model_train.Meta.check)
+        self.gen = next(_pack_generation)
         for side in ("encoder", "decoder"):
             for i, L in enumerate(getattr(model, side).layers):
                 a = L.self_attn
@@ -215,6 +273,10 @@ class DCTAutoencoder(nn.Module):
         self.proj_out = nn.Sequential(nn.LayerNorm(d, eps=1e-4), nn.Linear(d, pd, bias=False))
         self._packed: Optional[_Packed] = None
         self._packed_key = None
+        for _, linears in _packed_linears(self):
+            for lin in linears:
+                for q in lin.parameters(recurse=False):
+                    q.__class__ = _TrackedParameter
 
     # ---- reference helpers (modeling:86-117) ----
     def get_pos_embedding_decoder(self, dct_patches: DCTPatches):
@@ -257,8 +319,20 @@ class DCTAutoencoder(nn.Module):
     def _ctx(t):
         return _lib.context(t.device)
 
+    def _param_key(self):
+        return tuple(_param_stamp(p) for p in self.parameters())
+
+    def _install_packed(self, pk: _Packed):
+        """optim.FusedAdamW(model=self): the pack its kernel has just written is the current
+        one for the parameters as they are now; any later change of a parameter
+        (load_state_dict, an in-place op, a write through .data, another optimizer) rebuilds
+        it with torch ops."""
+        pk.gen = next(_pack_generation)
+        self._packed = pk
+        self._packed_key = self._param_key()
+
     def _weights(self) -> _Packed:
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        key = self._param_key()
         if self._packed is None or self._packed_key != key or (self.training and not self._packed.training):
             self._packed = _Packed(self)
             self._packed_key = key

@@ -173,6 +173,7 @@ class Meta:
 
     def __init__(self, pk, dp, heads, tabs):
         self.pk = pk
+        self.gen = pk.gen
         self.r, self.s = dp.key_pad_mask.shape
         self.heads = heads
         self.ids = dp.batched_image_ids.long().contiguous()
@@ -180,6 +181,13 @@ class Meta:
         self.ch = dp.patch_channels.reshape(-1).long().contiguous()
         self.pos = dp.patch_positions.reshape(-1, 2).long().contiguous()
         self.rows_h, self.rows_w, self.rows_c = (t.shape[0] for t in tabs)
+
+    def check(self):
+        """Every backward reads pk.wt: refuse a pack that an optimizer step has rewritten in
+        place since the forward (for torch-op packs autograd's version check does the same)."""
+        if self.pk.gen != self.gen:
+            raise RuntimeError("backward through a stale graph: the optimizer step rewrote the packed bf16 weights "
+                               "this forward used (run the forward again after optimizer.step())")
 
 
 # ---- autograd ----
@@ -207,6 +215,7 @@ class LayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        ctx.meta.check()
         h, a1, qkv, o, lse, hm, a2, pre, f, ln1w, ln2w = ctx.saved_tensors
         meta, name, eps, inter = ctx.meta, ctx.name, ctx.eps, ctx.inter
         pk = meta.pk
@@ -260,6 +269,7 @@ class EmbedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh):
+        ctx.meta.check()
         xb, e, lnw = ctx.saved_tensors
         meta, pd = ctx.meta, ctx.pd
         m, d = e.shape
@@ -288,6 +298,7 @@ class PosAddFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        ctx.meta.check()
         dy = dy.float().contiguous()
         return (dy, None) + _pos_grads(dy, ctx.meta)
 
@@ -307,6 +318,7 @@ class ProjOutFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        ctx.meta.check()
         h, a, lnw = ctx.saved_tensors
         meta, pd = ctx.meta, ctx.pd
         m, d = h.shape

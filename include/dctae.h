@@ -637,6 +637,60 @@ int dctae_model_qgelu_bwd(dctae_ctx* ctx, int64_t M, int32_t N, const uint16_t* 
 int dctae_model_pos_grad(dctae_ctx* ctx, int64_t M, int32_t D, const float* g_dev, int64_t ldg, const int64_t* idx_dev,
                          int64_t idx_stride, int32_t rows, float* out_dev, void* stream);
 
+/* ---- fused optimizer step (additive; ABI version unchanged) ----
+ * Gradient-norm clip (torch clip_grad_norm_), AdamW (torch.optim.AdamW's
+ * single-tensor arithmetic, fp32, separately rounded) and the bf16 weight
+ * packs of dctae_model_linear, over a device-resident segment table.  No
+ * floating-point atomics: a step repeats bit for bit. */
+
+/* One parameter tensor.  p / g / exp_avg / exp_avg_sq: (rows, cols) fp32,
+ * contiguous, 4-byte aligned (16-byte alignment is detected per segment and
+ * used).  1-D tensors: rows = 1.  A segment with w_dst or wt_dst is "packed"
+ * (walked in 64 x 64 tiles), any other "flat". */
+typedef struct {
+  float* p;
+  const float* g;
+  float* exp_avg;
+  float* exp_avg_sq;
+  uint16_t* w_dst;     /* bf16 pack, row-major: w_dst[(w_row_off + r) * ldw + c] = bf16(p[r][c]), or NULL */
+  uint16_t* wt_dst;    /* bf16 pack, transposed: wt_dst[c * ldwt + wt_col_off + r] = bf16(p[r][c]), or NULL */
+  float* copy_dst;     /* fp32 copy of the updated p (flat segments), or NULL */
+  int64_t rows, cols;
+  int64_t ldw, ldwt;   /* leading dimensions of the packs; elements past cols / rows are never written */
+  int64_t w_row_off, wt_col_off;
+  int64_t norm0, work0; /* filled by dctae_optim_plan: first gradient-norm block / first update work item */
+  int32_t group;       /* index into the groups of dctae_optim_adamw_pack */
+  int32_t reserved;
+} dctae_optim_seg;
+
+/* Per-group scalars, computed by the caller in double as torch does:
+ * decay = 1 - lr * weight_decay, w1 = 1 - beta1, w2 = 1 - beta2,
+ * step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t). */
+typedef struct {
+  float decay, w1, beta2, w2, step_size, bc2_sqrt, eps, reserved;
+} dctae_optim_group;
+
+#define DCTAE_OPTIM_MAX_GROUPS 16
+
+/* Host only (ctx may be NULL): checks a host copy of the table and fills
+ * norm0 / work0; the totals size the two launches and the workspace. */
+int dctae_optim_plan(dctae_ctx* ctx, dctae_optim_seg* segs_host, int32_t count, int64_t* n_norm_blocks,
+                     int64_t* n_work);
+
+/* stats_dev[0] = (float)sqrt(sum g^2) over the table (squares and sums in
+ * fp64, fixed order); stats_dev[1] = min(1, max_norm / (stats_dev[0] + 1e-6f)),
+ * NaN kept.  ws_dev: n_norm_blocks doubles. */
+int dctae_optim_gradnorm(dctae_ctx* ctx, const dctae_optim_seg* segs_dev, int32_t count, int64_t n_norm_blocks,
+                         float max_norm, double* ws_dev, float* stats_dev, void* stream);
+
+/* Per element: g' = g * coef; p *= decay; m = lerp(m, g', w1);
+ * v = v * beta2 + w2 * g' * g'; p -= step_size * m / (sqrt(v) / bc2_sqrt + eps),
+ * then the packs and copies of the segment.  coef = stats_dev[1] read on the
+ * device, or 1 when stats_dev is NULL; g itself is not rewritten.  groups: host
+ * array of n_groups <= DCTAE_OPTIM_MAX_GROUPS. */
+int dctae_optim_adamw_pack(dctae_ctx* ctx, const dctae_optim_seg* segs_dev, int32_t count, int64_t n_work,
+                           const dctae_optim_group* groups, int32_t n_groups, const float* stats_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
