@@ -10,7 +10,7 @@ from .dct_patches import DCTPatches, build_attn_mask, from_dict, to_dict  # noqa
 from .feature_extraction import DCTAutoencoderFeatureExtractor, GroupPatchesState  # noqa: F401
 from .lfq import LFQ  # noqa: F401
 from .losses import (LFQDistance, calculate_perplexity, compute_entropy_loss, masked_mean,  # noqa: F401
-                     masked_perplexity, reconstruction_losses, step_losses)
+                     masked_perplexity, pixel_loss, reconstruction_losses, step_losses)
 from .model import CLIPEncoderConfig, DCTAutoencoder, DCTAutoencoderConfig  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
 from .patchnorm import PatchNorm  # noqa: F401
@@ -22,4 +22,4 @@ __all__ = ["DCTAutoencoderFeatureExtractor", "DCTPatches", "PatchNorm", "LFQ", "
            "DCTAutoencoder", "DCTAutoencoderConfig", "CLIPEncoderConfig", "FusedAdamW",
            "GroupPatchesState", "build_attn_mask", "load_library", "DCTAEError", "DCTAEUnavailable",
            "LFQDistance", "compute_entropy_loss", "masked_mean", "calculate_perplexity",
-           "reconstruction_losses", "masked_perplexity", "step_losses"]
+           "reconstruction_losses", "masked_perplexity", "step_losses", "pixel_loss"]

@@ -546,42 +546,120 @@ def vq_from_indices(cfg: VQCfg, idx: torch.Tensor, project_out: bool) -> torch.T
     return out
 
 
+class DecodeTable:
+    """The host-side image table of one packed batch (the descriptor arguments
+    of dctae_decode / dctae_decode_backward / dctae_pixel_loss_forward) and
+    the batch tensors in the layout the library reads.  Building it walks
+    ``ids.cpu()``: the one host synchronisation of a decode."""
+
+    def __init__(self, p: FEParams, ids, key_pad, positions, channels, patch_sizes, original_sizes):
+        self.dev = _check_dev(ids, key_pad, positions, channels)
+        self.R, self.S = ids.shape
+        self.ids = ids.long().contiguous()
+        self.key_pad = key_pad.to(torch.bool).contiguous()
+        self.pos = positions.long().contiguous()
+        self.ch = channels.long().contiguous()
+        # image enumeration: rows in order, ids ascending (FE:619-633); host view
+        ids_h = self.ids.cpu()
+        self.lut_w = int(ids_h.max().item()) + 1 if ids_h.numel() else 1
+        lut = [-1] * (self.R * self.lut_w)
+        n_img = 0
+        for r in range(self.R):
+            for im in torch.unique(ids_h[r]).tolist():
+                lut[r * self.lut_w + im] = n_img
+                n_img += 1
+        if n_img > len(patch_sizes) or n_img > len(original_sizes):
+            raise IndexError("more images in the batch than patch_sizes / original_sizes entries")
+        self.n_img = n_img
+        self.hw, self.phw, self.offs = [], [], []
+        total = 0
+        for i in range(n_img):
+            h, w = (int(v) for v in original_sizes[i])
+            ph, pw = (int(v) for v in patch_sizes[i])
+            self.hw += [h, w]
+            self.phw += [ph, pw]
+            self.offs.append(total)
+            total += p.channels * h * w
+        self.total = total
+        self.channels = p.channels
+        self.keep = [i32(lut), i32(self.hw), i64(self.offs), i32(self.phw)]
+
+    def c_args(self):
+        """img_lut, lut_w, n_img, out_hw, out_off, patch_hw as the C ABI takes them"""
+        k = self.keep
+        return (C.cast(k[0], C.POINTER(C.c_int32)), self.lut_w, self.n_img, C.cast(k[1], C.POINTER(C.c_int32)),
+                C.cast(k[2], C.POINTER(C.c_int64)), C.cast(k[3], C.POINTER(C.c_int32)))
+
+    def images(self, flat: torch.Tensor) -> List[torch.Tensor]:
+        """the (3, H, W) views of a flat buffer in the decode's output layout"""
+        return [flat[o: o + self.channels * self.hw[2 * i] * self.hw[2 * i + 1]].view(
+            self.channels, self.hw[2 * i], self.hw[2 * i + 1]) for i, o in enumerate(self.offs)]
+
+
+def decode_table(p: FEParams, ids, key_pad, positions, channels, patch_sizes, original_sizes) -> DecodeTable:
+    return DecodeTable(p, ids, key_pad, positions, channels, patch_sizes, original_sizes)
+
+
+def pixel_loss_forward(table: DecodeTable, rgb_hat: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
+    """dctae_pixel_loss_forward on two flat image buffers in the decode's output
+    layout: (1 + n_img) fp32 on the device = [pixel_loss, mse_0 ...]."""
+    dev = _check_dev(rgb_hat, rgb)
+    for t in (rgb_hat, rgb):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != table.total:
+            raise AssertionError("pixel loss: the image buffers must be contiguous fp32 in the decode's layout")
+    ctx = _lib.context(dev)
+    sc = torch.empty(1 + table.n_img, dtype=torch.float32, device=dev)
+    _, _, n_img, hw, off, _ = table.c_args()
+    rc = ctx.lib.dctae_pixel_loss_forward(ctx.h, n_img, hw, off, ptr(rgb_hat), ptr(rgb), ptr(sc), _lib.stream_ptr(dev))
+    ctx.check(rc, "dctae_pixel_loss_forward")
+    return sc
+
+
+def decode_backward(p: FEParams, table: DecodeTable, patches: torch.Tensor, grad_rgb: Optional[torch.Tensor] = None,
+                    rgb_hat: Optional[torch.Tensor] = None, rgb: Optional[torch.Tensor] = None,
+                    g: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dctae_decode_backward: the gradient of the decode's images with respect
+    to ``patches`` (R, S, PP), fp32.  Upstream either ``grad_rgb`` (flat, the
+    decode's output layout) or the pixel loss's (``rgb_hat``, ``rgb``, the
+    flat buffers of pixel_loss_forward, and ``g``, the loss's upstream
+    gradient, one fp32 on the device)."""
+    dev = _check_dev(patches, grad_rgb, rgb_hat, rgb, g)
+    pp = patches.detach().float().contiguous()
+    if tuple(pp.shape) != (table.R, table.S, p.patch_size ** 2):
+        raise AssertionError(f"patches {tuple(pp.shape)} do not match the batch ({table.R}, {table.S}, "
+                             f"{p.patch_size ** 2})")
+    flats = [grad_rgb] if grad_rgb is not None else [rgb_hat, rgb]
+    if any(t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != table.total for t in flats):
+        raise AssertionError("decode backward: the image buffers must be contiguous fp32 in the decode's layout")
+    if grad_rgb is None:
+        g = g.detach().to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+    ctx = _lib.context(dev)
+    dp = torch.empty_like(pp)
+    rc = ctx.lib.dctae_decode_backward(ctx.h, C.byref(p.c(table.S)), table.R, *table.c_args(), ptr(table.ids),
+                                       ptr(table.key_pad), ptr(table.pos), ptr(table.ch), ptr(pp), ptr(grad_rgb),
+                                       ptr(rgb_hat), ptr(rgb), ptr(g if grad_rgb is None else None), ptr(dp),
+                                       _lib.stream_ptr(dev))
+    ctx.check(rc, "dctae_decode_backward")
+    return dp
+
+
 def decode(p: FEParams, ids: torch.Tensor, key_pad: torch.Tensor, positions: torch.Tensor, channels: torch.Tensor,
            patch_sizes: Sequence, original_sizes: Sequence, codes: Optional[torch.Tensor] = None,
            patches: Optional[torch.Tensor] = None, norm: Optional[NormState] = None,
-           lfq: Optional[LFQCfg] = None, normed: bool = False) -> List[torch.Tensor]:
+           lfq: Optional[LFQCfg] = None, normed: bool = False, table: Optional[DecodeTable] = None,
+           return_flat: bool = False) -> List[torch.Tensor]:
     """dctae_decode; returns a list of (3, H, W) fp32 device images.  normed:
     patches are PatchNorm outputs and the inverse_norm runs inside the decode
-    (dctae_decode_normed; norm required, no codes)."""
+    (dctae_decode_normed; norm required, no codes).  table: the batch's
+    DecodeTable when the caller already built it; return_flat: also the flat
+    buffer the images are views of, as (images, flat)."""
     dev = _check_dev(ids, key_pad, positions, channels, codes, patches)
+    if table is None:
+        table = decode_table(p, ids, key_pad, positions, channels, patch_sizes, original_sizes)
     ctx = _lib.context(dev)
-    R, S = ids.shape
-    ids_c = ids.long().contiguous()
-    kp = key_pad.to(torch.bool).contiguous()
-    pos = positions.long().contiguous()
-    ch = channels.long().contiguous()
-    # image enumeration: rows in order, ids ascending (FE:619-633); host view
-    ids_h = ids_c.cpu()
-    lut_w = int(ids_h.max().item()) + 1 if ids_h.numel() else 1
-    lut = [-1] * (R * lut_w)
-    n_img = 0
-    for r in range(R):
-        for im in torch.unique(ids_h[r]).tolist():
-            lut[r * lut_w + im] = n_img
-            n_img += 1
-    if n_img > len(patch_sizes) or n_img > len(original_sizes):
-        raise IndexError("more images in the batch than patch_sizes / original_sizes entries")
-    hw, phw, offs = [], [], []
-    total = 0
-    for i in range(n_img):
-        h, w = (int(v) for v in original_sizes[i])
-        ph, pw = (int(v) for v in patch_sizes[i])
-        hw += [h, w]
-        phw += [ph, pw]
-        offs.append(total)
-        total += p.channels * h * w
-    out = torch.empty(total, dtype=torch.float32, device=dev)
-    keep = [i32(lut), i32(hw), i64(offs), i32(phw)]
+    R, S, ids_c, kp, pos, ch = table.R, table.S, table.ids, table.key_pad, table.pos, table.ch
+    lut_w, n_img, hw, offs, keep = table.lut_w, table.n_img, table.hw, table.offs, table.keep
+    out = torch.empty(table.total, dtype=torch.float32, device=dev)
     cc = codes.long().contiguous() if codes is not None else None
     pp = patches.float().contiguous() if patches is not None else None
     nc = norm.c() if norm is not None else None
@@ -606,7 +684,7 @@ def decode(p: FEParams, ids: torch.Tensor, key_pad: torch.Tensor, positions: tor
     for i in range(n_img):
         h, w = hw[2 * i], hw[2 * i + 1]
         imgs.append(out[offs[i]: offs[i] + p.channels * h * w].view(p.channels, h, w))
-    return imgs
+    return (imgs, out) if return_flat else imgs
 
 
 def dct2(x: torch.Tensor, inverse: bool, color: bool) -> torch.Tensor:

@@ -5,6 +5,7 @@
 //   dctae_plan.hip     DCT matrices, GEMM problems and tile lists, FFT / Bluestein plans
 //   dctae_encode.hip   the encode plan and launch sequence
 //   dctae_decode.hip   the decode launch sequences
+//   dctae_decode_bwd.hip  the decode's backward and the pixel loss (kernels and launch sequence)
 //   dctae_api_ops.hip  PatchNorm, LFQ, VectorQuantize and transformer entry points
 #pragma once
 #include <cmath>

@@ -364,12 +364,24 @@ class DCTAutoencoderFeatureExtractor:
                 images.append(img)
         return images
 
-    @torch.no_grad()
     def postprocess(self, x: DCTPatches) -> List[torch.Tensor]:
         """FE:289-310: un-normalised DCTPatches -> RGB images (revert_patching,
         zero pad, DCT-III, IPT -> RGB fused on the GPU).  With an overridden
         _transform_image_out / revert_patching the reference's stage sequence
-        runs through the hooks (e.g. the spectrum itself for decode_gif.py:86-91)."""
+        runs through the hooks (e.g. the spectrum itself for decode_gif.py:86-91).
+
+        Differentiable in the patches: patches that require grad (with grad
+        enabled) give the same images, bit for bit, with a grad_fn whose
+        backward is dctae_decode_backward; fp16 / bf16 patches are upcast to
+        fp32 and the gradient is cast back.  The staged-hook path stays
+        without a grad_fn."""
+        if x.patches.requires_grad and torch.is_grad_enabled() and x.patches.is_cuda and not self._staged_out():
+            from . import losses
+            return losses.differentiable_postprocess(self, x)
+        return self._postprocess_no_grad(x)
+
+    @torch.no_grad()
+    def _postprocess_no_grad(self, x: DCTPatches) -> List[torch.Tensor]:
         if self._staged_out():
             images = []
             for image, (h, w) in zip(self.revert_patching(x), x.original_sizes):

@@ -22,7 +22,9 @@ Differences from the reference, both deliberate:
 The other two terms of the reference's training step (main.py:44-93) are
 here as well: ``reconstruction_losses`` (the masked L1 pair on the normalized
 and the inverse-normalized output, fused HIP forward and backward on a GPU),
-``masked_perplexity`` and ``step_losses``, the dict of main.py:85-93.
+``masked_perplexity`` and ``step_losses``, the dict of main.py:85-93; with
+``decode_pixels`` also ``pixel_loss`` (main.py:95-110), the mean per-image MSE
+of the decoded images, over a differentiable decode (dctae_decode_backward).
 """
 from __future__ import annotations
 
@@ -241,11 +243,122 @@ def masked_perplexity(codes, mask, codebook_size):
     return calculate_perplexity(torch.where(m, codes, torch.full_like(codes, -1)), codebook_size)
 
 
-def step_losses(res, batch, normalized_batch, patchnorm, codebook_size, training=True):
-    """The dict the reference's step_autoencoder returns (main.py:85-93, without
-    decode_pixels) from the model's output ``res`` (``dct_patches``, ``codes``,
-    ``commit_loss``, ``distances``), the raw ``batch`` and the
-    ``normalized_batch`` it was fed."""
+class _Postprocess(torch.autograd.Function):
+    """FE.postprocess with a HIP backward (dctae_decode / dctae_decode_backward):
+    the images of ``patches`` and, in the backward, the vjp of the upstream
+    image gradients.  Nothing is saved but the patches: the backward recomputes
+    the pre-colour image with the colour-less GEMM inverse."""
+
+    @staticmethod
+    def forward(ctx, patches, table, params):
+        imgs, _ = _ops.decode(params, table.ids, table.key_pad, table.pos, table.ch, None, None, patches=patches,
+                              table=table, return_flat=True)
+        ctx.save_for_backward(patches)
+        ctx.args = (table, params)
+        ctx.set_materialize_grads(False)
+        return tuple(imgs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        patches, = ctx.saved_tensors
+        table, params = ctx.args
+        if all(g is None for g in grads):
+            return None, None, None
+        flat = torch.zeros(table.total, dtype=torch.float32, device=patches.device)
+        for view, g in zip(table.images(flat), grads):
+            if g is not None:
+                view.copy_(g)
+        dp = _ops.decode_backward(params, table, patches, grad_rgb=flat)
+        return dp.view(patches.shape).to(patches.dtype), None, None
+
+
+def _decode_table(proc, dp):
+    return _ops.decode_table(proc.params(dp.patches.shape[1]), dp.batched_image_ids, dp.key_pad_mask,
+                             dp.patch_positions, dp.patch_channels, dp.patch_sizes, dp.original_sizes)
+
+
+def differentiable_postprocess(proc, dp):
+    """``proc.postprocess(dp)`` (fused path) with a grad_fn: what
+    DCTAutoencoderFeatureExtractor.postprocess runs for patches that require grad."""
+    return list(_Postprocess.apply(dp.patches, _decode_table(proc, dp), proc.params(dp.patches.shape[1])))
+
+
+class _PixelLoss(torch.autograd.Function):
+    """The two decodes, dctae_pixel_loss_forward and, in the backward,
+    dctae_decode_backward in its fused form (the gradient image
+    g 2 (x_hat - x) / (3 H W n_img) exists only inside the colour kernel).
+    One image table (its ids.cpu() walk is the only host synchronisation)
+    serves all three calls."""
+
+    @staticmethod
+    def forward(ctx, patches, target_patches, table, params):
+        def dec(x):
+            return _ops.decode(params, table.ids, table.key_pad, table.pos, table.ch, None, None, patches=x,
+                               table=table, return_flat=True)
+        x_hat, flat_hat = dec(patches)
+        x, flat = dec(target_patches)
+        sc = _ops.pixel_loss_forward(table, flat_hat, flat)
+        ctx.save_for_backward(patches, flat_hat, flat)
+        ctx.args = (table, params)
+        ctx.mark_non_differentiable(*x_hat, *x)
+        return (sc[0].clone(), *x_hat, *x)
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        patches, flat_hat, flat = ctx.saved_tensors
+        table, params = ctx.args
+        dp = _ops.decode_backward(params, table, patches, rgb_hat=flat_hat, rgb=flat, g=g)
+        return dp.view(patches.shape).to(patches.dtype), None, None, None
+
+
+def pixel_loss(output_unnormalized, target_unnormalized, proc):
+    """The pixel term of the reference's step_autoencoder (main.py:96-106),
+    arguments ``DCTPatches`` of un-normalised patches over the same packed batch:
+
+        images_hat = proc.postprocess(output_unnormalized)
+        images     = proc.postprocess(target_unnormalized)
+        pixel_loss = mean_i F.mse_loss(images[i], images_hat[i])
+
+    Returns (pixel_loss, images_hat, images): a 0-d fp32 device tensor and two
+    lists of (3, H, W) fp32 images.  pixel_loss carries the gradient to
+    ``output_unnormalized.patches`` (fused HIP forward and backward); the
+    target gets none.
+
+    Differences from the reference, all deliberate:
+      * the returned images are detached: a further loss on ``images_hat``
+        takes ``proc.postprocess`` of patches that require grad instead;
+      * fp16 / bf16 patches are upcast to fp32 and the gradient is cast back;
+      * padded tokens are never read, their gradient is exactly zero;
+      * with an overridden ``_transform_image_out`` / ``revert_patching`` hook
+        the staged stages run and the loss is torch ops on their images, which
+        carry no grad_fn (as ``postprocess`` itself there)."""
+    import torch.nn.functional as F
+    out = output_unnormalized.patches
+    if proc._staged_out() or not out.is_cuda:
+        if not out.is_cuda:
+            from ._lib import DCTAEUnavailable
+            raise DCTAEUnavailable("pixel_loss: the decode has no CPU path")
+        x_hat, x = proc.postprocess(output_unnormalized), proc.postprocess(target_unnormalized)
+        loss = sum(F.mse_loss(a, b) for a, b in zip(x, x_hat)) / len(x_hat)
+        return loss, x_hat, x
+    table = _decode_table(proc, output_unnormalized)
+    params = proc.params(out.shape[1])
+    res = _PixelLoss.apply(out, target_unnormalized.patches.detach(), table, params)
+    n = table.n_img
+    return res[0], list(res[1:1 + n]), list(res[1 + n:])
+
+
+def step_losses(res, batch, normalized_batch, patchnorm, codebook_size, training=True, decode_pixels=False,
+                proc=None):
+    """The dict the reference's step_autoencoder returns (main.py:85-112) from
+    the model's output ``res`` (``dct_patches``, ``codes``, ``commit_loss``,
+    ``distances``), the raw ``batch`` and the ``normalized_batch`` it was fed.
+    decode_pixels (main.py:95-110, needs the feature extractor ``proc``): adds
+    ``x_hat``, ``pixel_loss`` and ``x``, the target decoded from
+    ``inverse_norm(normalized_batch)`` as the reference does; pixel_loss reaches
+    ``res["dct_patches"].patches`` through rec_patches_unnormalized."""
+    if decode_pixels and proc is None:
+        raise ValueError("step_losses(decode_pixels=True) needs proc, the feature extractor that decodes the images")
     output = res["dct_patches"]
     mask = ~output.key_pad_mask
     entropy_loss = compute_entropy_loss(res["distances"], mask) if training else 0.0
@@ -254,9 +367,15 @@ def step_losses(res, batch, normalized_batch, patchnorm, codebook_size, training
         perplexity = masked_perplexity(res["codes"], mask, codebook_size)
     unnormalized = output.shallow_copy()
     unnormalized.patches = un
-    return dict(rec_patches=output, rec_patches_unnormalized=unnormalized, rec_loss=rec_loss,
-                rec_loss_unnormalized=rec_loss_unnormalized, perplexity=perplexity,
-                commit_loss=res["commit_loss"], entropy_loss=entropy_loss)
+    out = dict(rec_patches=output, rec_patches_unnormalized=unnormalized, rec_loss=rec_loss,
+               rec_loss_unnormalized=rec_loss_unnormalized, perplexity=perplexity,
+               commit_loss=res["commit_loss"], entropy_loss=entropy_loss)
+    if decode_pixels:
+        target = normalized_batch.shallow_copy()
+        with torch.no_grad():
+            target.patches = patchnorm.inverse_norm(normalized_batch)
+        out["pixel_loss"], out["x_hat"], out["x"] = pixel_loss(unnormalized, target, proc)
+    return out
 
 
 def calculate_perplexity(codes, codebook_size, null_index=-1):

@@ -423,6 +423,42 @@ int dctae_decode_normed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows,
                         const int64_t* positions_dev, const int64_t* channels_dev, const dctae_norm* norm,
                         const float* normed_patches_dev, float* rgb_dev, void* stream);
 
+/* Gradient of dctae_decode's images with respect to patches_dev (the patches
+ * form: codes_dev == NULL, no PatchNorm), in place of autograd through
+ * FE.postprocess (FE:289-310): colour adjoint -> transposed DCT GEMMs truncated
+ * to the kept corner -> the adjoint of revert_patching.  The descriptor
+ * arguments are dctae_decode's.  The upstream gradient is either
+ *   grad_rgb_dev   (3,H,W) per image in rgb_dev's layout (the generic vjp), or,
+ *   with grad_rgb_dev == NULL, the pixel loss's own: rgb_hat_dev and rgb_dev
+ *   (dctae_pixel_loss_forward's two buffers) and g_dev, one fp32 on the
+ *   device, the upstream gradient of pixel_loss; the gradient image
+ *   g 2 (x_hat - x) / (3 H_i W_i n_img) is formed in the colour kernel and
+ *   never stored.
+ * The pre-colour image the colour adjoint needs is recomputed from
+ * patches_dev by the colour-less GEMM inverse (on every geometry, 512 x 512
+ * included); the forward saves nothing.  dpatches_dev (n_rows, S, P*P): every
+ * element is written -- the token's tile of the spectrum gradient where the
+ * token owns its place (of two real tokens at one place the later packed slot,
+ * FE:639-643), exact zeros at padding and at the overwritten token, NaN at a
+ * token the forward flags (which also sets the context's index error,
+ * dctae_check_device_errors).  Nothing synchronises with the host beyond the
+ * plan upload every decode has; bit-identical from run to run. */
+int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut,
+                          int32_t lut_w, int32_t n_img, const int32_t* out_hw, const int64_t* out_off,
+                          const int32_t* patch_hw, const int64_t* image_ids_dev, const uint8_t* key_pad_dev,
+                          const int64_t* positions_dev, const int64_t* channels_dev, const float* patches_dev,
+                          const float* grad_rgb_dev, const float* rgb_hat_dev, const float* rgb_dev,
+                          const float* g_dev, float* dpatches_dev, void* stream);
+
+/* The pixel loss of the reference's step_autoencoder (main.py:100-106) on two
+ * image sets in dctae_decode's output layout (out_hw / out_off, host, per
+ * image): scalars_dev (1 + n_img floats) = pixel_loss = mean_i mse_i, then
+ * mse_i = mean((rgb_hat_i - rgb_i)^2).  A thread's terms are added in fp32,
+ * block partials (double, in the workspace) in a fixed order by one block: no
+ * floating-point atomics, bit-identical from run to run.  n_img = 0 gives NaN. */
+int dctae_pixel_loss_forward(dctae_ctx* ctx, int32_t n_img, const int32_t* out_hw, const int64_t* out_off,
+                             const float* rgb_hat_dev, const float* rgb_dev, float* scalars_dev, void* stream);
+
 /* thr[e] = the smallest fp32 x with PatchNorm(x)[e] > 0, for the n table
  * elements (patchnorm.py:157-165 is monotone in x for a positive std), so
  * that the LFQ bit of a token element is exactly (x >= thr[e]); NaN = never.
