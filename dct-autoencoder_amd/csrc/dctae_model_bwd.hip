@@ -470,7 +470,10 @@ __global__ void k_qgelu_bwd(const uint16_t* df, int64_t lddf, const uint16_t* pr
   const int n = (int)(i - m * N);
   const float x = bf2f(pre[m * ldp + n]);
   const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.45546696228f * x));
-  dpre[m * lddp + n] = f2bf(bf2f(df[m * lddf + n]) * (sg * (1.0f + 1.702f * x * (1.0f - sg))));
+  // beyond +-64 sg is exactly 1 or 0 and the derivative exactly 1 or 0; x itself would overflow 1.702 x
+  // from 2e38 on (inf * 0): the clamp changes no finite result
+  const float xc = fminf(fmaxf(x, -64.0f), 64.0f);
+  dpre[m * lddp + n] = f2bf(bf2f(df[m * lddf + n]) * (sg * (1.0f + 1.702f * xc * (1.0f - sg))));
 }
 
 void launch_qgelu(const uint16_t* pre, int64_t ldp, int64_t M, int N, uint16_t* out, int64_t ldo, hipStream_t s) {

@@ -60,6 +60,7 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.detach().float().contiguous()
 
 LIN_F32, LIN_BF16, LIN_BF16_QGELU, LIN_F32_RESIDUAL = 0, 1, 2, 3
+LN_BWD_MAX_D = 2048   # dctae_model_layernorm_bwd's widest row (the forward LayerNorm takes 4096)
 
 
 @dataclass
@@ -351,6 +352,10 @@ class DCTAutoencoder(nn.Module):
             c = getattr(self.config, side)
             if c.dropout != 0 or c.attention_dropout != 0:
                 raise NotImplementedError(f"{side}: dropout / attention_dropout != 0 has no kernel in training")
+        d = self.config.encoder_config.hidden_size
+        if d > LN_BWD_MAX_D:
+            raise NotImplementedError(f"hidden_size={d}: the LayerNorm backward kernel takes rows of at most "
+                                      f"{LN_BWD_MAX_D} (the forward, and so .eval(), takes 4096)")
 
     def _check_mode(self, dp: Optional[DCTPatches] = None):
         if self.training:
