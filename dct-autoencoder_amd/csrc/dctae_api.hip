@@ -289,9 +289,13 @@ int dctae_check_device_errors(dctae_ctx* ctx, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   int h = 0;
+  // a flag raised by the context's previous ordered call on another stream is
+  // read only after that call, and a later call's flag is raised after the clear
+  order_after_previous(ctx, s);
   HIPCHK(ctx, hipMemcpyAsync(&h, ctx->err_dev, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   HIPCHK(ctx, hipMemsetAsync(ctx->err_dev, 0, sizeof(int), s));
+  mark_done(ctx, s);
   if (h & 1) return fail(ctx, DCTAE_EINVAL, "channel/position index out of range of the PatchNorm tables");
   if (h & 2) return fail(ctx, DCTAE_EINVAL, "batched_image_ids entry has no image (patch_sizes mismatch)");
   if (h & 4) return fail(ctx, DCTAE_EINVAL, "token position outside its image's patch grid");

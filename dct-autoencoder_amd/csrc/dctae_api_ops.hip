@@ -13,6 +13,7 @@ int dctae_norm_thresholds(dctae_ctx* ctx, const dctae_norm* norm, int64_t n, flo
   if (!norm || !norm->median_dev || !norm->b_dev || !thr_dev || n < 0)
     return fail(ctx, DCTAE_EINVAL, "bad threshold arguments");
   hipStream_t s = (hipStream_t)stream;
+  order_after_previous(ctx, s);   // clears and reads the shared ctx->err_dev
   HIPCHK(ctx, hipMemsetAsync(ctx->err_dev, 0, sizeof(int), s));
   launch_norm_thresholds(norm->median_dev, norm->b_dev, n, norm->eps, norm->min_val, norm->max_val, thr_dev,
                          ctx->err_dev, s);
@@ -21,6 +22,7 @@ int dctae_norm_thresholds(dctae_ctx* ctx, const dctae_norm* norm, int64_t n, flo
   HIPCHK(ctx, hipMemcpyAsync(&h, ctx->err_dev, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   HIPCHK(ctx, hipMemsetAsync(ctx->err_dev, 0, sizeof(int), s));
+  mark_done(ctx, s);
   if (h) return fail(ctx, DCTAE_EUNSUP, "negative PatchNorm std: thresholds undefined (use thr_dev = NULL)");
   return 0;
 }
@@ -84,10 +86,14 @@ int dctae_rec_loss_forward(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, in
   if (n > 0 && (!out || !tn || !raw || !ch || !pos || !key_pad)) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
   if (int rc = ensure_ws(ctx, rec_loss_ws_bytes(n, P * P), 256)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  Timer t(ctx, s, "rec_loss_forward");
-  launch_rec_loss_fwd(out, tn, raw, ch, pos, key_pad, n, P * P, mh, mw, norm->median_dev, norm->b_dev, norm->eps,
-                      unnorm, ctx->ws, scalars, ctx->err_dev, s);
+  order_after_previous(ctx, s);   // the block partials live in the shared ctx->ws
+  {
+    Timer t(ctx, s, "rec_loss_forward");
+    launch_rec_loss_fwd(out, tn, raw, ch, pos, key_pad, n, P * P, mh, mw, norm->median_dev, norm->b_dev, norm->eps,
+                        unnorm, ctx->ws, scalars, ctx->err_dev, s);
+  }
   HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
   return 0;
 }
 
@@ -118,8 +124,7 @@ struct StatsScratch {
   float *t0, *t1;  // two (n_cells, PP) tables (batch median / batch b)
 };
 
-int stats_scratch(dctae_ctx* ctx, int64_t n_tok, int n_cells, int PP, bool tables, hipStream_t s,
-                  StatsScratch* o) {
+int stats_scratch(dctae_ctx* ctx, int64_t n_tok, int n_cells, int PP, bool tables, StatsScratch* o) {
   auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t b_tok = al(sizeof(int32_t) * std::max<int64_t>(n_tok, 1));
   const size_t b_cell = al(sizeof(int32_t) * n_cells);
@@ -127,7 +132,8 @@ int stats_scratch(dctae_ctx* ctx, int64_t n_tok, int n_cells, int PP, bool table
   const size_t need = 2 * b_tok + 3 * b_cell + 2 * b_tab;
   if (need > ctx->st_bytes) {
     if (ctx->st_ws) {
-      HIPCHK(ctx, hipStreamSynchronize(s));
+      // the previous user may have run on another stream (as vq_scratch / proj_scratch)
+      HIPCHK(ctx, hipDeviceSynchronize());
       HIPCHK(ctx, hipFree(ctx->st_ws));
       ctx->st_ws = nullptr;
       ctx->st_bytes = 0;
@@ -172,11 +178,15 @@ int dctae_norm_batch_stats(dctae_ctx* ctx, int32_t P, int32_t C, int32_t mh, int
   hipStream_t s = (hipStream_t)stream;
   const int n_cells = C * mh * mw, PP = P * P;
   StatsScratch w;
-  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, false, s, &w)) return rc;
-  Timer t(ctx, s, "norm_batch_stats");
-  launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
-  launch_stats_median(x, PP, n_cells, w.start, w.count, w.list, batch_median, batch_n, s);
+  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, false, &w)) return rc;
+  order_after_previous(ctx, s);   // shared ctx->st_ws
+  {
+    Timer t(ctx, s, "norm_batch_stats");
+    launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
+    launch_stats_median(x, PP, n_cells, w.start, w.count, w.list, batch_median, batch_n, s);
+  }
   HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
   return 0;
 }
 
@@ -188,11 +198,15 @@ int dctae_norm_batch_mad(dctae_ctx* ctx, int32_t P, int32_t C, int32_t mh, int32
   hipStream_t s = (hipStream_t)stream;
   const int n_cells = C * mh * mw, PP = P * P;
   StatsScratch w;
-  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, false, s, &w)) return rc;
-  Timer t(ctx, s, "norm_batch_mad");
-  launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
-  launch_stats_batch_b(x, PP, n_cells, w.start, w.count, w.list, median, batch_b, s);
+  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, false, &w)) return rc;
+  order_after_previous(ctx, s);   // shared ctx->st_ws
+  {
+    Timer t(ctx, s, "norm_batch_mad");
+    launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
+    launch_stats_batch_b(x, PP, n_cells, w.start, w.count, w.list, median, batch_b, s);
+  }
   HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
   return 0;
 }
 
@@ -220,7 +234,8 @@ int dctae_norm_train_step(dctae_ctx* ctx, const dctae_norm* norm, float* n_dev, 
   float* median = const_cast<float*>(norm->median_dev);
   float* b = const_cast<float*>(norm->b_dev);
   StatsScratch w;
-  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, true, s, &w)) return rc;
+  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, true, &w)) return rc;
+  order_after_previous(ctx, s);   // shared ctx->st_ws
   Timer t(ctx, s, "norm_train_step");
   launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
   launch_stats_median(x, PP, n_cells, w.start, w.count, w.list, w.t0, w.bn, s);      // :112-130
@@ -233,6 +248,7 @@ int dctae_norm_train_step(dctae_ctx* ctx, const dctae_norm* norm, float* n_dev, 
     else if (y != x) HIPCHK(ctx, hipMemcpyAsync(y, x, sizeof(float) * n_tok * PP, hipMemcpyDeviceToDevice, s));
   }
   HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
   return 0;
 }
 
@@ -287,10 +303,14 @@ int dctae_lfq_entropy_forward(dctae_ctx* ctx, const dctae_lfq* lfq, const float*
                       256)))
     return rc;
   hipStream_t s = (hipStream_t)stream;
-  Timer t(ctx, s, "lfq_entropy_forward");
-  launch_lfq_entropy_fwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature, eps,
-                         ctx->ws, avg_probs, scalars, s);
+  order_after_previous(ctx, s);   // the partial histograms live in the shared ctx->ws
+  {
+    Timer t(ctx, s, "lfq_entropy_forward");
+    launch_lfq_entropy_fwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature,
+                           eps, ctx->ws, avg_probs, scalars, s);
+  }
   HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
   return 0;
 }
 
@@ -305,11 +325,15 @@ int dctae_lfq_entropy_backward(dctae_ctx* ctx, const dctae_lfq* lfq, const float
   if (n_tok == 0) return 0;
   if ((rc = ensure_ws(ctx, sizeof(float) * lfq_entropy_bwd_ws_floats(lfq->codebook_dim), 256))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  Timer t(ctx, s, "lfq_entropy_backward");
-  if (launch_lfq_entropy_bwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature,
-                             eps, avg_probs, scalars, grad, ctx->ws, dh, s))
-    return fail(ctx, DCTAE_EHIP, "LFQ entropy backward: the kernel's LDS size could not be set");
+  order_after_previous(ctx, s);   // shared ctx->ws
+  {
+    Timer t(ctx, s, "lfq_entropy_backward");
+    if (launch_lfq_entropy_bwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature,
+                               eps, avg_probs, scalars, grad, ctx->ws, dh, s))
+      return fail(ctx, DCTAE_EHIP, "LFQ entropy backward: the kernel's LDS size could not be set");
+  }
   HIPCHK(ctx, hipGetLastError());
+  mark_done(ctx, s);
   return 0;
 }
 

@@ -19,6 +19,11 @@
  *  - All work is enqueued on `stream` (a hipStream_t, passed as void*; NULL =
  *    legacy default stream).  The library never synchronises the host, except
  *    when it must grow its internal workspace or upload a new plan.
+ *  - A context may be driven from several streams of its device: every call
+ *    that uses the context's own device memory (workspace, staging, plan,
+ *    scratch, error flag read-out) is ordered after the context's previous
+ *    call on another stream by an event, with no host wait; the caller orders
+ *    only its own tensors (DESIGN.md "Streams and the context's scratch").
  *  - Every call returns 0 on success and a negative DCTAE_E* code on error;
  *    dctae_last_error(ctx) describes the last error of that context.
  *  - One context per device per host thread (not re-entrant).
