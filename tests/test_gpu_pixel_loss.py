@@ -86,11 +86,13 @@ def case(pkg, name):
     return proc, dp, t, ws
 
 
-def check_per_image(name, what, got, key, floor_rel):
-    """got: fp32 gradient (R, S, PP) against the fixture's float64 entry, image by image"""
+def check_per_image(name, what, got, g32, g64, img, floor_rel):
+    """got: fp32 gradient (R, S, PP) against the float64 oracle g64, image by image (img: the image
+    of every slot, -1 at padding); g32 is the oracle's own fp32 run, the yardstick.  Returns
+    (dev, ref, allowance, max |g|) of every image."""
     got = got.detach().double().cpu().numpy()
-    g32, g64 = G[f"{name}_{key}_f32"].astype(np.float64), G[f"{name}_{key}_f64"]
-    img = token_image(name).numpy()
+    g32, g64, img = np.asarray(g32, dtype=np.float64), np.asarray(g64), np.asarray(img)
+    rows = []
     for i in range(int(img.max()) + 1):
         sel = img == i
         dev, ref = np.abs(got[sel] - g64[sel]).max(), np.abs(g32[sel] - g64[sel]).max()
@@ -98,6 +100,14 @@ def check_per_image(name, what, got, key, floor_rel):
         print(f"{name} {what} image {i}: kernel dev {dev:.3e} reference fp32 dev {ref:.3e} allowance {tol:.3e} "
               f"(max |g| {np.abs(g64[sel]).max():.3e})")
         assert dev <= tol, f"{name} {what} image {i}: {dev:.3e} > {tol:.3e}"
+        rows.append((dev, ref, tol, np.abs(g64[sel]).max()))
+    return rows
+
+
+def check_fixture(name, what, got, key, floor_rel):
+    """check_per_image against the recorded entries ``key`` of the fixture"""
+    check_per_image(name, what, got, G[f"{name}_{key}_f32"], G[f"{name}_{key}_f64"], token_image(name).numpy(),
+                    floor_rel)
 
 
 def step_setup(pkg):
@@ -164,7 +174,7 @@ def test_vjp_against_the_reference(pkg, name):
     imgs = proc.postprocess(dp(out))
     g, = torch.autograd.grad(sum((w * im).sum() for w, im in zip(ws, imgs)), out)
     assert g.dtype == torch.float32 and g.shape == out.shape
-    check_per_image(name, "vjp", g, "vjp", 2e-6)
+    check_fixture(name, "vjp", g, "vjp", 2e-6)
     assert torch.all(g[t["key_pad"]] == 0), "gradient at padded tokens must be exactly zero"
     ops().check_device_errors(out.device)
 
@@ -192,7 +202,7 @@ def test_pixel_loss(pkg, name):
     assert abs(loss.item() - l64) <= tol
     # (c) the gradient against the reference's float64 gradient
     g, = torch.autograd.grad(loss, out)
-    check_per_image(name, "pixel-loss grad", g, "grad", 2e-6)
+    check_fixture(name, "pixel-loss grad", g, "grad", 2e-6)
     # (d) the fused backward against the generic route
     o2 = t["out"].clone().requires_grad_(True)
     xh2 = proc.postprocess(dp(o2))
@@ -238,12 +248,9 @@ def test_structure(pkg, name):
     ops().check_device_errors(out.device)
 
 
-@pytest.mark.parametrize("poison", [0, 1])
-@pytest.mark.parametrize("name", ["ragged14", "p5", "sq512"])
-def test_bit_identical_runs(pkg, name, poison):
-    """through autograd (whose thread has a context of its own) and through the
+def bit_identical_runs(pkg, proc, dp, t, poison):
+    """two runs through autograd (whose thread has a context of its own) and through the
     library calls on this thread, where the option is set"""
-    proc, dp, t, _ = case(pkg, name)
     ops().set_option("ws_poison", poison)
     try:
         runs = []
@@ -261,8 +268,16 @@ def test_bit_identical_runs(pkg, name, poison):
         ops().set_option("ws_poison", 0)
     for a, b in zip(*runs):
         assert torch.equal(a, b)
-    loss, g, sc, d1, _ = runs[0]
+    loss, g, sc, d1, d2 = runs[0]
     assert torch.isfinite(loss) and torch.equal(sc[0], loss) and torch.equal(d1, g)
+    return g, d2
+
+
+@pytest.mark.parametrize("poison", [0, 1])
+@pytest.mark.parametrize("name", ["ragged14", "p5", "sq512"])
+def test_bit_identical_runs(pkg, name, poison):
+    proc, dp, t, _ = case(pkg, name)
+    bit_identical_runs(pkg, proc, dp, t, poison)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

@@ -1,20 +1,22 @@
 """CPU side of the pixel loss (main.py:95-110): the fixture of
 tests/golden/pixel_loss_ref*.npz (gen_pixel_loss_golden.py) is pinned by
-oracle.ref_cpu under autograd -- in fp32 it reproduces the reference's recorded
-losses and gradients exactly, and the float64 recipe (revert_patching with the
-per-token loop, zero pad, idct2, ipt_to_rgb on double tensors) reproduces the
-``_f64`` entries -- so the GPU test's oracle rests on code that travels with
-the repository.  Also: the structure of the recorded gradients, the step's
+oracle.ref_cpu under autograd (the recipe of oracle.decode_cases) -- in fp32 it
+reproduces the reference's recorded losses and gradients exactly, and the
+float64 recipe (revert_patching with the per-token loop, zero pad, idct2,
+ipt_to_rgb on double tensors) reproduces the ``_f64`` entries -- so the GPU
+tests' oracle, at the recorded shapes and at those of decode_cases.CASES, rests
+on code that travels with the repository.  Also: the structure of the recorded gradients, the step's
 argument check and the C ABI's two new entry points."""
 import os
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import ROOT, golden
+from oracle import decode_cases as oracle
 from oracle import ref_cpu
+from oracle.decode_cases import upstream
 
 G = {}
 for _f in ("pixel_loss_ref.npz", "pixel_loss_ref_sq512.npz", "pixel_loss_ref_sq512_f64.npz"):
@@ -24,11 +26,6 @@ NAMES = [str(n) for n in G["names"]]
 CFG = {n: (int(p), int(m[0]), int(m[1]), int(s)) for n, p, m, s in
        zip(NAMES, G["patch_size"], G["max_patch"], G["max_seq_len"])}
 SYMBOLS = ("dctae_decode_backward", "dctae_pixel_loss_forward")
-
-
-def upstream(a, u, v):
-    """w[c, y, x] = fp32(sum_r a[r, c] u[r, y] v[r, x]), the sum in float64 (as the generator)"""
-    return torch.einsum("rc,ry,rx->cyx", a.double(), u.double(), v.double()).float()
 
 
 def case(name):
@@ -45,51 +42,15 @@ def case(name):
     return batch, t["out"], ws, ref_cpu.FEConfig(patch_size=P, max_patch_h=mh, max_patch_w=mw, max_seq_len=S)
 
 
-def ipt_to_rgb(x):
-    """ref_cpu.ipt_to_rgb (util.py:85-97) with the colour matrices the fixture was recorded with
-    (colors.npz): ref_cpu.color_matrices() recomputes rgb2lms.inverse() in fp32 on the host it runs
-    on, and another CPU gives other last bits (5.8e-5 on ragged14's vjp, measured)"""
-    m = golden("colors.npz")
-    l = ref_cpu._channel_mult(torch.from_numpy(m["ipt2lms"].copy()), x)
-    return ref_cpu._channel_mult(torch.from_numpy(m["lms2rgb"].copy()), ref_cpu._signed_pow(l, 1 / ref_cpu.IPT_GAMMA))
-
-
-def oracle_images(batch, cfg, patches):
-    """FE:289-310 with ref_cpu's dtype-keeping stages"""
-    b = ref_cpu.Batch(patches=patches, key_pad_mask=batch.key_pad_mask, attn_mask=None,
-                      batched_image_ids=batch.batched_image_ids, patch_channels=batch.patch_channels,
-                      patch_positions=batch.patch_positions, patch_sizes=batch.patch_sizes,
-                      original_sizes=batch.original_sizes)
-    out = []
-    for img, (h, w) in zip(ref_cpu.revert_patching(b, cfg, per_token_loop=True), batch.original_sizes):
-        full = torch.zeros(cfg.channels, h, w, dtype=img.dtype)
-        full[:, : img.shape[1], : img.shape[2]] = img
-        out.append(ipt_to_rgb(ref_cpu.idct2(full)))
-    return out
-
-
 def oracle_results(name, dtype):
     batch, out, ws, cfg = case(name)
-    out = out.to(dtype).requires_grad_(True)
-    with torch.no_grad():
-        x = oracle_images(batch, cfg, batch.patches.to(dtype))
-    x_hat = oracle_images(batch, cfg, out)
-    loss = sum(F.mse_loss(a, b) for a, b in zip(x, x_hat)) / len(x_hat)
-    grad, = torch.autograd.grad(loss, out, retain_graph=True)
-    vjp, = torch.autograd.grad(sum((w.to(dtype) * xh).sum() for w, xh in zip(ws, x_hat)), out)
-    return loss.detach().numpy(), grad.numpy(), vjp.numpy()
+    r = oracle.oracle_results(batch, cfg, out, ws, dtype)
+    return r["loss"], r["grad"], r["vjp"]
 
 
 def token_image(name):
-    """image index of every packed slot (-1 at padding): rows in order, ids ascending (FE:619-633)"""
-    ids, kp = torch.from_numpy(G[f"{name}_ids"]).long(), torch.from_numpy(G[f"{name}_key_pad"])
-    img = torch.full(ids.shape, -1, dtype=torch.long)
-    n = 0
-    for r in range(ids.shape[0]):
-        for i in torch.unique(ids[r]).tolist():
-            img[r][(ids[r] == i) & ~kp[r]] = n
-            n += 1
-    return img
+    """image index of every packed slot of the recorded batch (-1 at padding)"""
+    return oracle.token_image(G[f"{name}_ids"], G[f"{name}_key_pad"])
 
 
 @pytest.mark.parametrize("name", NAMES)
