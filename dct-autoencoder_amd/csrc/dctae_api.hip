@@ -50,65 +50,59 @@ void default_colors(ColorMats& cm) {
   }
 }
 
-// the call-ordering event (order_after_previous / mark_done) only orders this
-// context's calls across streams of one device: no system-scope fence (its
-// cache write-back sat between back-to-back calls)
+// the call-ordering event (OrderedCall) only orders this context's calls
+// across streams of one device: no system-scope fence (its cache write-back
+// sat between back-to-back calls)
 constexpr unsigned kDoneEvtFlags = hipEventDisableTiming | hipEventDisableSystemFence;
+
+constexpr const char* kScratchName[kNumScratch] = {"workspace", "staging", "PatchNorm statistics scratch",
+                                                   "VectorQuantize scratch", "LFQ projection scratch"};
 
 }  // namespace
 
-int dctae::upload_plan(dctae_ctx* ctx, const PlanBuf& pb, hipStream_t s, uint64_t plan_id) {
+int OrderedCall::upload(const PlanBuf& pb, uint8_t** base, uint64_t plan_id) {
   const size_t n = pb.bytes.size();
+  *base = ctx->plan.p;
   if (n == 0) return 0;
   if (plan_id != 0 && plan_id == ctx->plan_last_id) return 0;
   if (n == ctx->plan_last.size() && std::memcmp(pb.bytes.data(), ctx->plan_last.data(), n) == 0) {
     ctx->plan_last_id = plan_id;
     return 0;
   }
-  if (n > ctx->plan_cap) {
-    HIPCHK(ctx, hipDeviceSynchronize());
+  if (n > ctx->plan.cap) {
+    // both copies go and come back together; a failure leaves no device copy and nothing cached
+    const size_t cap = std::max<size_t>(n * 2, 1 << 20);
+    ctx->plan_last.clear();
+    ctx->plan_last_id = 0;
+    HIPCHK(ctx, hipDeviceSynchronize());   // no upload still reads plan_host
     if (ctx->plan_host) hipHostFree(ctx->plan_host);
-    if (ctx->plan_dev) hipFree(ctx->plan_dev);
     ctx->plan_host = nullptr;
-    ctx->plan_dev = nullptr;
-    size_t cap = std::max<size_t>(n * 2, 1 << 20);
+    ctx->plan.release();
     HIPCHK(ctx, hipHostMalloc((void**)&ctx->plan_host, cap, hipHostMallocDefault));
-    HIPCHK(ctx, hipMalloc((void**)&ctx->plan_dev, cap));
-    ctx->plan_cap = cap;
+    if (int rc = ctx->plan.grow(ctx, cap, "plan")) return rc;
+    *base = ctx->plan.p;
   } else {
     HIPCHK(ctx, hipEventSynchronize(ctx->plan_evt));  // previous upload finished reading plan_host
   }
   std::memcpy(ctx->plan_host, pb.bytes.data(), n);
-  HIPCHK(ctx, hipMemcpyAsync(ctx->plan_dev, ctx->plan_host, n, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->plan.p, ctx->plan_host, n, hipMemcpyHostToDevice, s));
   HIPCHK(ctx, hipEventRecord(ctx->plan_evt, s));
   ctx->plan_last = pb.bytes;
   ctx->plan_last_id = plan_id;
   return 0;
 }
 
-int dctae::ensure_ws(dctae_ctx* ctx, size_t ws_bytes, size_t stage_bytes) {
-  if (ws_bytes > ctx->ws_bytes) {
+int OrderedCall::scratch_bytes(Scratch which, size_t bytes, uint8_t** out) {
+  DevBuf& b = ctx->scratch[which];
+  const bool grew = bytes > b.cap;
+  if (int rc = b.grow(ctx, bytes, kScratchName[which])) return rc;
+  *out = b.p;
+  // ws_poison: the workspace and the staging are filled when this call first
+  // asks for them (and when it grows them), never over what it wrote since
+  if (ctx->opt.ws_poison && which <= kStage && b.p && (grew || !(poisoned & (1u << which)))) {
+    poisoned |= 1u << which;
     HIPCHK(ctx, hipDeviceSynchronize());
-    if (ctx->ws) hipFree(ctx->ws);
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-    if (hipMalloc((void**)&ctx->ws, ws_bytes) != hipSuccess)
-      return fail(ctx, DCTAE_ENOMEM, "workspace allocation of " + std::to_string(ws_bytes) + " bytes failed");
-    ctx->ws_bytes = ws_bytes;
-  }
-  if (stage_bytes > ctx->stage_bytes) {
-    HIPCHK(ctx, hipDeviceSynchronize());
-    if (ctx->stage) hipFree(ctx->stage);
-    ctx->stage = nullptr;
-    ctx->stage_bytes = 0;
-    if (hipMalloc((void**)&ctx->stage, stage_bytes) != hipSuccess)
-      return fail(ctx, DCTAE_ENOMEM, "staging allocation of " + std::to_string(stage_bytes) + " bytes failed");
-    ctx->stage_bytes = stage_bytes;
-  }
-  if (ctx->opt.ws_poison) {   // a request of <= 256 bytes leaves that buffer alone (a call's second ensure_ws)
-    HIPCHK(ctx, hipDeviceSynchronize());
-    if (ws_bytes > 256) HIPCHK(ctx, hipMemset(ctx->ws, 0xff, ctx->ws_bytes));
-    if (stage_bytes > 256) HIPCHK(ctx, hipMemset(ctx->stage, 0xff, ctx->stage_bytes));
+    HIPCHK(ctx, hipMemset(b.p, 0xff, b.cap));
     HIPCHK(ctx, hipDeviceSynchronize());
   }
   return 0;
@@ -178,15 +172,11 @@ int dctae_ctx_destroy(dctae_ctx* ctx) {
     hipFree(kv.second.d);
     hipFree(kv.second.dh);
   }
-  if (ctx->ws) hipFree(ctx->ws);
-  if (ctx->stage) hipFree(ctx->stage);
+  for (DevBuf& b : ctx->scratch) b.release();
+  ctx->plan.release();
   if (ctx->plan_host) hipHostFree(ctx->plan_host);
-  if (ctx->plan_dev) hipFree(ctx->plan_dev);
   if (ctx->err_dev) hipFree(ctx->err_dev);
   if (ctx->fft_tab) hipFree(ctx->fft_tab);
-  if (ctx->st_ws) hipFree(ctx->st_ws);
-  if (ctx->vq_ws) hipFree(ctx->vq_ws);
-  if (ctx->proj_ws) hipFree(ctx->proj_ws);
   drop_encode_plan(ctx);
   for (auto& p : ctx->pending) {
     hipEventDestroy(p.a);
@@ -291,11 +281,10 @@ int dctae_check_device_errors(dctae_ctx* ctx, void* stream) {
   int h = 0;
   // a flag raised by the context's previous ordered call on another stream is
   // read only after that call, and a later call's flag is raised after the clear
-  order_after_previous(ctx, s);
+  OrderedCall oc(ctx, s);
   HIPCHK(ctx, hipMemcpyAsync(&h, ctx->err_dev, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   HIPCHK(ctx, hipMemsetAsync(ctx->err_dev, 0, sizeof(int), s));
-  mark_done(ctx, s);
   if (h & 1) return fail(ctx, DCTAE_EINVAL, "channel/position index out of range of the PatchNorm tables");
   if (h & 2) return fail(ctx, DCTAE_EINVAL, "batched_image_ids entry has no image (patch_sizes mismatch)");
   if (h & 4) return fail(ctx, DCTAE_EINVAL, "token position outside its image's patch grid");

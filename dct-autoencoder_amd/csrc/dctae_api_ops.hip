@@ -13,7 +13,7 @@ int dctae_norm_thresholds(dctae_ctx* ctx, const dctae_norm* norm, int64_t n, flo
   if (!norm || !norm->median_dev || !norm->b_dev || !thr_dev || n < 0)
     return fail(ctx, DCTAE_EINVAL, "bad threshold arguments");
   hipStream_t s = (hipStream_t)stream;
-  order_after_previous(ctx, s);   // clears and reads the shared ctx->err_dev
+  OrderedCall oc(ctx, s);   // clears and reads the shared ctx->err_dev
   HIPCHK(ctx, hipMemsetAsync(ctx->err_dev, 0, sizeof(int), s));
   launch_norm_thresholds(norm->median_dev, norm->b_dev, n, norm->eps, norm->min_val, norm->max_val, thr_dev,
                          ctx->err_dev, s);
@@ -22,7 +22,6 @@ int dctae_norm_thresholds(dctae_ctx* ctx, const dctae_norm* norm, int64_t n, flo
   HIPCHK(ctx, hipMemcpyAsync(&h, ctx->err_dev, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(ctx, hipStreamSynchronize(s));
   HIPCHK(ctx, hipMemsetAsync(ctx->err_dev, 0, sizeof(int), s));
-  mark_done(ctx, s);
   if (h) return fail(ctx, DCTAE_EUNSUP, "negative PatchNorm std: thresholds undefined (use thr_dev = NULL)");
   return 0;
 }
@@ -84,16 +83,14 @@ int dctae_rec_loss_forward(dctae_ctx* ctx, const dctae_norm* norm, int32_t P, in
   if (int rc = rec_loss_check(ctx, norm, P, mh, mw, n)) return rc;
   if (!scalars) return fail(ctx, DCTAE_EINVAL, "NULL output");
   if (n > 0 && (!out || !tn || !raw || !ch || !pos || !key_pad)) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
-  if (int rc = ensure_ws(ctx, rec_loss_ws_bytes(n, P * P), 256)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  order_after_previous(ctx, s);   // the block partials live in the shared ctx->ws
-  {
-    Timer t(ctx, s, "rec_loss_forward");
-    launch_rec_loss_fwd(out, tn, raw, ch, pos, key_pad, n, P * P, mh, mw, norm->median_dev, norm->b_dev, norm->eps,
-                        unnorm, ctx->ws, scalars, ctx->err_dev, s);
-  }
+  OrderedCall oc(ctx, s);
+  float* ws;   // the block partials
+  if (int rc = oc.scratch(kWs, rec_loss_ws_bytes(n, P * P), &ws)) return rc;
+  Timer t(ctx, s, "rec_loss_forward");
+  launch_rec_loss_fwd(out, tn, raw, ch, pos, key_pad, n, P * P, mh, mw, norm->median_dev, norm->b_dev, norm->eps,
+                      unnorm, ws, scalars, ctx->err_dev, s);
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -124,24 +121,13 @@ struct StatsScratch {
   float *t0, *t1;  // two (n_cells, PP) tables (batch median / batch b)
 };
 
-int stats_scratch(dctae_ctx* ctx, int64_t n_tok, int n_cells, int PP, bool tables, StatsScratch* o) {
+int stats_scratch(OrderedCall& oc, int64_t n_tok, int n_cells, int PP, bool tables, StatsScratch* o) {
   auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t b_tok = al(sizeof(int32_t) * std::max<int64_t>(n_tok, 1));
   const size_t b_cell = al(sizeof(int32_t) * n_cells);
   const size_t b_tab = tables ? al(sizeof(float) * (size_t)n_cells * PP) : 0;
-  const size_t need = 2 * b_tok + 3 * b_cell + 2 * b_tab;
-  if (need > ctx->st_bytes) {
-    if (ctx->st_ws) {
-      // the previous user may have run on another stream (as vq_scratch / proj_scratch)
-      HIPCHK(ctx, hipDeviceSynchronize());
-      HIPCHK(ctx, hipFree(ctx->st_ws));
-      ctx->st_ws = nullptr;
-      ctx->st_bytes = 0;
-    }
-    HIPCHK(ctx, hipMalloc((void**)&ctx->st_ws, need));
-    ctx->st_bytes = need;
-  }
-  uint8_t* p = ctx->st_ws;
+  uint8_t* p;
+  if (int rc = oc.scratch(kStats, 2 * b_tok + 3 * b_cell + 2 * b_tab, &p)) return rc;
   o->cell = (int32_t*)p;
   p += b_tok;
   o->list = (int32_t*)p;
@@ -177,16 +163,13 @@ int dctae_norm_batch_stats(dctae_ctx* ctx, int32_t P, int32_t C, int32_t mh, int
   if (!batch_n || !batch_median) return fail(ctx, DCTAE_EINVAL, "NULL output table");
   hipStream_t s = (hipStream_t)stream;
   const int n_cells = C * mh * mw, PP = P * P;
+  OrderedCall oc(ctx, s);
   StatsScratch w;
-  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, false, &w)) return rc;
-  order_after_previous(ctx, s);   // shared ctx->st_ws
-  {
-    Timer t(ctx, s, "norm_batch_stats");
-    launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
-    launch_stats_median(x, PP, n_cells, w.start, w.count, w.list, batch_median, batch_n, s);
-  }
+  if (int rc = stats_scratch(oc, n_tok, n_cells, PP, false, &w)) return rc;
+  Timer t(ctx, s, "norm_batch_stats");
+  launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
+  launch_stats_median(x, PP, n_cells, w.start, w.count, w.list, batch_median, batch_n, s);
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -197,16 +180,13 @@ int dctae_norm_batch_mad(dctae_ctx* ctx, int32_t P, int32_t C, int32_t mh, int32
   if (!median || !batch_b) return fail(ctx, DCTAE_EINVAL, "NULL table");
   hipStream_t s = (hipStream_t)stream;
   const int n_cells = C * mh * mw, PP = P * P;
+  OrderedCall oc(ctx, s);
   StatsScratch w;
-  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, false, &w)) return rc;
-  order_after_previous(ctx, s);   // shared ctx->st_ws
-  {
-    Timer t(ctx, s, "norm_batch_mad");
-    launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
-    launch_stats_batch_b(x, PP, n_cells, w.start, w.count, w.list, median, batch_b, s);
-  }
+  if (int rc = stats_scratch(oc, n_tok, n_cells, PP, false, &w)) return rc;
+  Timer t(ctx, s, "norm_batch_mad");
+  launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
+  launch_stats_batch_b(x, PP, n_cells, w.start, w.count, w.list, median, batch_b, s);
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -233,9 +213,9 @@ int dctae_norm_train_step(dctae_ctx* ctx, const dctae_norm* norm, float* n_dev, 
   const int n_cells = C * mh * mw, PP = P * P;
   float* median = const_cast<float*>(norm->median_dev);
   float* b = const_cast<float*>(norm->b_dev);
+  OrderedCall oc(ctx, s);
   StatsScratch w;
-  if (int rc = stats_scratch(ctx, n_tok, n_cells, PP, true, &w)) return rc;
-  order_after_previous(ctx, s);   // shared ctx->st_ws
+  if (int rc = stats_scratch(oc, n_tok, n_cells, PP, true, &w)) return rc;
   Timer t(ctx, s, "norm_train_step");
   launch_stats_lists(ch, pos, key_pad, n_tok, C, mh, mw, w.cell, w.count, w.start, w.list, ctx->err_dev, s);
   launch_stats_median(x, PP, n_cells, w.start, w.count, w.list, w.t0, w.bn, s);      // :112-130
@@ -248,7 +228,6 @@ int dctae_norm_train_step(dctae_ctx* ctx, const dctae_norm* norm, float* n_dev, 
     else if (y != x) HIPCHK(ctx, hipMemcpyAsync(y, x, sizeof(float) * n_tok * PP, hipMemcpyDeviceToDevice, s));
   }
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -299,18 +278,16 @@ int dctae_lfq_entropy_forward(dctae_ctx* ctx, const dctae_lfq* lfq, const float*
   int rc;
   if ((rc = lfq_entropy_check(ctx, lfq, h, mask, n_tok, temperature))) return rc;
   if (!avg_probs || !scalars) return fail(ctx, DCTAE_EINVAL, "NULL output");
-  if ((rc = ensure_ws(ctx, sizeof(float) * lfq_entropy_fwd_ws_floats(n_tok, lfq->num_codebooks, lfq->codebook_dim),
-                      256)))
-    return rc;
   hipStream_t s = (hipStream_t)stream;
-  order_after_previous(ctx, s);   // the partial histograms live in the shared ctx->ws
-  {
-    Timer t(ctx, s, "lfq_entropy_forward");
-    launch_lfq_entropy_fwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature,
-                           eps, ctx->ws, avg_probs, scalars, s);
-  }
+  OrderedCall oc(ctx, s);
+  float* ws;   // the partial histograms
+  if ((rc = oc.scratch(kWs, sizeof(float) * lfq_entropy_fwd_ws_floats(n_tok, lfq->num_codebooks, lfq->codebook_dim),
+                       &ws)))
+    return rc;
+  Timer t(ctx, s, "lfq_entropy_forward");
+  launch_lfq_entropy_fwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature, eps,
+                         ws, avg_probs, scalars, s);
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -323,17 +300,15 @@ int dctae_lfq_entropy_backward(dctae_ctx* ctx, const dctae_lfq* lfq, const float
   if ((rc = lfq_entropy_check(ctx, lfq, h, mask, n_tok, temperature))) return rc;
   if (!avg_probs || !scalars || !grad || (n_tok > 0 && !dh)) return fail(ctx, DCTAE_EINVAL, "NULL tensor");
   if (n_tok == 0) return 0;
-  if ((rc = ensure_ws(ctx, sizeof(float) * lfq_entropy_bwd_ws_floats(lfq->codebook_dim), 256))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  order_after_previous(ctx, s);   // shared ctx->ws
-  {
-    Timer t(ctx, s, "lfq_entropy_backward");
-    if (launch_lfq_entropy_bwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature,
-                               eps, avg_probs, scalars, grad, ctx->ws, dh, s))
-      return fail(ctx, DCTAE_EHIP, "LFQ entropy backward: the kernel's LDS size could not be set");
-  }
+  OrderedCall oc(ctx, s);
+  float* ws;
+  if ((rc = oc.scratch(kWs, sizeof(float) * lfq_entropy_bwd_ws_floats(lfq->codebook_dim), &ws))) return rc;
+  Timer t(ctx, s, "lfq_entropy_backward");
+  if (launch_lfq_entropy_bwd(h, mask, n_tok, lfq->num_codebooks, lfq->codebook_dim, lfq->codebook_scale, temperature,
+                             eps, avg_probs, scalars, grad, ws, dh, s))
+    return fail(ctx, DCTAE_EHIP, "LFQ entropy backward: the kernel's LDS size could not be set");
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -374,17 +349,13 @@ static int lfq_project_in_impl(dctae_ctx* ctx, const dctae_lfq* lfq, const float
   if (int rc = lfq_proj_check(ctx, lfq, n, dim, x, w, idx, 64)) return rc;
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = proj_scratch(ctx, lfq->codebook_dim * lfq->num_codebooks, dim)) return rc;
-  // ctx->proj_ws (the pre-split weight) is shared with every call of this
-  // context: ordered after the previous call, whatever its stream
-  order_after_previous(ctx, s);
-  {
-    Timer t(ctx, s, "lfq_project_in");
-    launch_lfq_project_in(x, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, idx,
-                          ctx->proj_ws, s, ctx->opt.gemm_h2 ? x_bound : 0.0f, ctx->opt.lfq_ws != 0);
-  }
+  OrderedCall oc(ctx, s);
+  uint16_t* wsp;   // the pre-split weight
+  if (int rc = oc.scratch(kProj, lfq_proj_scratch_bytes(lfq->codebook_dim * lfq->num_codebooks, dim), &wsp)) return rc;
+  Timer t(ctx, s, "lfq_project_in");
+  launch_lfq_project_in(x, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, idx, wsp, s,
+                        ctx->opt.gemm_h2 ? x_bound : 0.0f, ctx->opt.lfq_ws != 0);
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -406,16 +377,14 @@ int dctae_lfq_project_out(dctae_ctx* ctx, const dctae_lfq* lfq, const int64_t* i
   if (int rc = lfq_proj_check(ctx, lfq, n, dim, idx, w, out, 32, true)) return rc;
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = proj_scratch(ctx, dim, lfq->codebook_dim * lfq->num_codebooks)) return rc;
-  order_after_previous(ctx, s);   // shared ctx->proj_ws
-  {
-    Timer t(ctx, s, "lfq_project_out");
-    launch_lfq_project_out(idx, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out,
-                           ctx->proj_ws, s, nullptr, nullptr, nullptr, nullptr, 0.f, 0, 0, nullptr, ctx->opt.gemm_h2 != 0,
-                           ctx->opt.lfq_ws != 0);
-  }
+  OrderedCall oc(ctx, s);
+  uint16_t* wsp;
+  if (int rc = oc.scratch(kProj, lfq_proj_scratch_bytes(dim, lfq->codebook_dim * lfq->num_codebooks), &wsp)) return rc;
+  Timer t(ctx, s, "lfq_project_out");
+  launch_lfq_project_out(idx, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out, wsp, s,
+                         nullptr, nullptr, nullptr, nullptr, 0.f, 0, 0, nullptr, ctx->opt.gemm_h2 != 0,
+                         ctx->opt.lfq_ws != 0);
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -434,16 +403,14 @@ int dctae_lfq_project_out_inverse_norm(dctae_ctx* ctx, const dctae_lfq* lfq, con
     return fail(ctx, DCTAE_EINVAL, "fused inverse PatchNorm needs 16-byte aligned median / b / out");
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = proj_scratch(ctx, dim, lfq->codebook_dim * lfq->num_codebooks)) return rc;
-  order_after_previous(ctx, s);   // shared ctx->proj_ws
-  {
-    Timer t(ctx, s, "lfq_project_out");
-    launch_lfq_project_out(idx, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out,
-                           ctx->proj_ws, s, channels, positions, norm->median_dev, norm->b_dev, norm->eps, max_patch_h,
-                           max_patch_w, ctx->err_dev, ctx->opt.gemm_h2 != 0, ctx->opt.lfq_ws != 0);
-  }
+  OrderedCall oc(ctx, s);
+  uint16_t* wsp;
+  if (int rc = oc.scratch(kProj, lfq_proj_scratch_bytes(dim, lfq->codebook_dim * lfq->num_codebooks), &wsp)) return rc;
+  Timer t(ctx, s, "lfq_project_out");
+  launch_lfq_project_out(idx, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out, wsp, s,
+                         channels, positions, norm->median_dev, norm->b_dev, norm->eps, max_patch_h, max_patch_w,
+                         ctx->err_dev, ctx->opt.gemm_h2 != 0, ctx->opt.lfq_ws != 0);
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -460,21 +427,11 @@ static int vq_check(dctae_ctx* ctx, const dctae_vq* vq) {
   return 0;
 }
 
-static int vq_scratch(dctae_ctx* ctx, size_t need) {
-  if (need <= ctx->vq_bytes) return 0;
-  HIPCHK(ctx, hipDeviceSynchronize());
-  if (ctx->vq_ws) hipFree(ctx->vq_ws);
-  ctx->vq_ws = nullptr;
-  ctx->vq_bytes = 0;
-  if (hipMalloc((void**)&ctx->vq_ws, need) != hipSuccess)
-    return fail(ctx, DCTAE_ENOMEM, "VectorQuantize scratch allocation of " + std::to_string(need) + " bytes failed");
-  ctx->vq_bytes = need;
-  return 0;
-}
-
 // O (n, N) = A (n, K) W^T (N, K) + bias, on k_gemm_f32 (plan uploaded through the shared plan buffer)
-static int vq_linear(dctae_ctx* ctx, const float* A, int64_t n, int K, const float* W, const float* bias, int N,
-                     float* O, const uint8_t* mask, const float* orig, hipStream_t s, const char* name) {
+static int vq_linear(OrderedCall& oc, const float* A, int64_t n, int K, const float* W, const float* bias, int N,
+                     float* O, const uint8_t* mask, const float* orig, const char* name) {
+  dctae_ctx* ctx = oc.ctx;
+  const hipStream_t s = oc.s;
   // k_gemm_x3 addresses each operand through a buffer resource with a 32-bit
   // byte range: the rows go in chunks whose A and O spans stay below 2^31 bytes
   const int64_t rows_max = ((int64_t)1 << 31) / ((int64_t)4 * std::max(K, N)) - 1;
@@ -488,10 +445,10 @@ static int vq_linear(dctae_ctx* ctx, const float* A, int64_t n, int K, const flo
   PlanBuf pb;
   const size_t g_off = pb.add(g.data(), g.size());
   const size_t t_off = pb.add(t.data(), t.size());
-  int rc;
-  if ((rc = upload_plan(ctx, pb, s))) return rc;
+  uint8_t* pd;
+  if (int rc = oc.upload(pb, &pd)) return rc;
   Timer tm(ctx, s, name);
-  ctx_gemm(ctx, 1, (const GemmProblem*)(ctx->plan_dev + g_off), (const TileRef*)(ctx->plan_dev + t_off), (int)t.size(), s);
+  ctx_gemm(ctx, 1, (const GemmProblem*)(pd + g_off), (const TileRef*)(pd + t_off), (int)t.size(), s);
   launch_vq_bias(O, bias, n, N, mask, orig, s);
   return 0;
 }
@@ -517,9 +474,10 @@ int dctae_vq_forward(dctae_ctx* ctx, const dctae_vq* vq, const float* x, const u
   const size_t y2_b = ((size_t)C * 4 + 255) & ~size_t(255);
   const size_t v_b = ((size_t)nv * D * 4 + 255) & ~size_t(255);
   const bool need_xq = quantize != nullptr;
-  if ((rc = vq_scratch(ctx, acc_b + et_b + y2_b + (proj ? v_b : 0) + ((need_xq && (proj || mask)) ? v_b : 0))))
+  OrderedCall oc(ctx, s);
+  uint8_t* p;
+  if ((rc = oc.scratch(kVq, acc_b + et_b + y2_b + (proj ? v_b : 0) + ((need_xq && (proj || mask)) ? v_b : 0), &p)))
     return rc;
-  uint8_t* p = ctx->vq_ws;
   double* acc = (double*)p;
   float* et = (float*)(p + acc_b);
   float* y2 = (float*)(p + acc_b + et_b);
@@ -528,9 +486,8 @@ int dctae_vq_forward(dctae_ctx* ctx, const dctae_vq* vq, const float* x, const u
   if (proj) q += v_b;
   // codes: straight into quantize when nothing follows them
   float* xq = need_xq ? ((proj || mask) ? (float*)q : quantize) : nullptr;
-  order_after_previous(ctx, s);
-  if (proj && (rc = vq_linear(ctx, x, n_tok, vq->dim, vq->w_in_dev, vq->b_in_dev, HD, xp, nullptr, nullptr, s,
-                              "vq_project_in")))
+  if (proj &&
+      (rc = vq_linear(oc, x, n_tok, vq->dim, vq->w_in_dev, vq->b_in_dev, HD, xp, nullptr, nullptr, "vq_project_in")))
     return rc;
   {
     Timer t(ctx, s, "vq_codebook");
@@ -547,8 +504,7 @@ int dctae_vq_forward(dctae_ctx* ctx, const dctae_vq* vq, const float* x, const u
   }
   if (need_xq) {
     if (proj) {
-      if ((rc = vq_linear(ctx, xq, n_tok, HD, vq->w_out_dev, vq->b_out_dev, vq->dim, quantize, mask, x, s,
-                          "vq_project_out")))
+      if ((rc = vq_linear(oc, xq, n_tok, HD, vq->w_out_dev, vq->b_out_dev, vq->dim, quantize, mask, x, "vq_project_out")))
         return rc;
     } else if (mask) {
       HIPCHK(ctx, hipMemcpyAsync(quantize, xq, sizeof(float) * nv * D, hipMemcpyDeviceToDevice, s));
@@ -556,7 +512,6 @@ int dctae_vq_forward(dctae_ctx* ctx, const dctae_vq* vq, const float* x, const u
     }
   }
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -586,18 +541,16 @@ int dctae_vq_output_from_indices(dctae_ctx* ctx, const dctae_vq* vq, const int64
   hipStream_t s = (hipStream_t)stream;
   const int HD = vq->heads * vq->codebook_dim;
   if (vq->dim == HD) return dctae_vq_codes_from_indices(ctx, vq, idx, n, out, stream);
-  if ((rc = vq_scratch(ctx, ((size_t)n * HD * 4 + 255) & ~size_t(255)))) return rc;
-  float* codes = (float*)ctx->vq_ws;
-  order_after_previous(ctx, s);
+  OrderedCall oc(ctx, s);
+  float* codes;
+  if ((rc = oc.scratch(kVq, ((size_t)n * HD * 4 + 255) & ~size_t(255), &codes))) return rc;
   {
     Timer t(ctx, s, "vq_codes");
     launch_vq_codes(idx, n * vq->heads, vq->embed_dev, vq->codebook_size, codes, ctx->err_dev, s);
   }
-  if ((rc = vq_linear(ctx, codes, n, HD, vq->w_out_dev, vq->b_out_dev, vq->dim, out, nullptr, nullptr, s,
-                      "vq_project_out")))
+  if ((rc = vq_linear(oc, codes, n, HD, vq->w_out_dev, vq->b_out_dev, vq->dim, out, nullptr, nullptr, "vq_project_out")))
     return rc;
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 

@@ -1,7 +1,8 @@
 // The context behind the C ABI and what its host units share: error
-// reporting, per-launch timing, plan upload, workspace, and the planning
-// helpers of dctae_plan.hip.  Host code only (no kernels).
-//   dctae_api.hip      context, options, timing, plan upload, workspace
+// reporting, per-launch timing, the ordered call scope through which every
+// call reaches the context's scratch, and the planning helpers of
+// dctae_plan.hip.  Host code only (no kernels).
+//   dctae_api.hip      context, options, timing, scratch growth and plan upload
 //   dctae_plan.hip     DCT matrices, GEMM problems and tile lists, FFT / Bluestein plans
 //   dctae_encode.hip   the encode plan and launch sequence
 //   dctae_decode.hip   the decode launch sequences
@@ -31,6 +32,28 @@ struct TimingEntry {
   int64_t launches = 0;
 };
 
+namespace dctae {
+
+class OrderedCall;
+
+// a grow-only device buffer of the context
+struct DevBuf {
+  uint8_t* p = nullptr;
+  size_t cap = 0;
+  // at least `need` bytes; growing waits for the whole device before it frees
+  int grow(dctae_ctx* ctx, size_t need, const char* what);
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// the scratch buffers successive calls share (OrderedCall::scratch)
+enum Scratch { kWs, kStage, kStats, kVq, kProj, kNumScratch };
+
+}  // namespace dctae
+
 struct dctae_ctx {
   int device = 0;
   std::string err;
@@ -45,24 +68,10 @@ struct dctae_ctx {
     int hexp;
   };
   std::map<const float*, X3Mat> dct_x3;
-  // workspace (floats) and token staging (bytes), grow-only
-  float* ws = nullptr;
-  size_t ws_bytes = 0;
-  uint8_t* stage = nullptr;
-  size_t stage_bytes = 0;
-  // plan: host (pinned) + device copies, last uploaded plan bytes for caching
-  uint8_t* plan_host = nullptr;
-  uint8_t* plan_dev = nullptr;
-  size_t plan_cap = 0;
-  std::vector<uint8_t> plan_last;
-  uint64_t plan_last_id = 0, plan_counter = 0;
-  hipEvent_t plan_evt = nullptr;
-  hipEvent_t done_evt = nullptr;
+  uint64_t plan_counter = 0;   // ids of cached plans (OrderedCall::upload)
   // the encode's side stream (SideStream in dctae_encode.hip; created on first use)
   hipStream_t side = nullptr;
   hipEvent_t side_in = nullptr, side_out = nullptr;
-  hipStream_t last_stream = nullptr;
-  bool have_done = false;
   int* err_dev = nullptr;
   dctae::ColorMats cm{};
   // FFT-DCT plans: tables (W_M^k, alpha/beta) in one device buffer
@@ -73,25 +82,33 @@ struct dctae_ctx {
   std::map<int, int64_t> bs_tw;              // L -> offset of W_L^m in fft_tab
   size_t lds_limit = 64 * 1024;              // dynamic LDS the FFT kernels may use
   int n_cu = 256;
-  // PatchNorm training scratch (token cell ids, per-cell lists, batch tables), grow-only
-  uint8_t* st_ws = nullptr;
-  size_t st_bytes = 0;
-  // VectorQuantize scratch (projected vectors, codes, transformed codebook), grow-only
-  uint8_t* vq_ws = nullptr;
-  size_t vq_bytes = 0;
-  // LFQ projection scratch (the pre-split weight planes), grow-only
-  uint16_t* proj_ws = nullptr;
-  size_t proj_bytes = 0;
   // cached encode plan: valid for enc_key (the call's inputs and the
-  // plan-shaping options) while the workspace stays at enc_ws
+  // plan-shaping options) while the workspace stays where the plan was built (EncPlan::ws)
   std::vector<int64_t> enc_key;
-  const float* enc_ws = nullptr;
   struct EncPlan* enc_plan = nullptr;
   // timing
   bool timing = false;
   std::vector<TimedLaunch> pending;
   std::vector<hipEvent_t> evt_pool;
   std::vector<TimingEntry> totals;
+
+ private:
+  // What successive calls reuse, reachable only through an open OrderedCall:
+  // the scratch buffers (workspace; token staging; PatchNorm statistics; the
+  // VectorQuantize vectors, codes and codebook; the LFQ projections' pre-split
+  // weight), the plan (pinned host and device copies, the last uploaded bytes
+  // for caching) and the event that orders one call after the previous one.
+  friend class dctae::OrderedCall;
+  friend int ::dctae_ctx_create(int, dctae_ctx**);
+  friend int ::dctae_ctx_destroy(dctae_ctx*);
+  dctae::DevBuf scratch[dctae::kNumScratch], plan;
+  uint8_t* plan_host = nullptr;
+  std::vector<uint8_t> plan_last;
+  uint64_t plan_last_id = 0;
+  hipEvent_t plan_evt = nullptr;
+  hipEvent_t done_evt = nullptr;
+  hipStream_t last_stream = nullptr;
+  bool have_done = false;
 };
 
 namespace dctae {
@@ -154,16 +171,53 @@ struct PlanBuf {
   }
 };
 
-// order this call after the previous one on a possibly different stream
-inline void order_after_previous(dctae_ctx* ctx, hipStream_t s) {
-  if (ctx->have_done && ctx->last_stream != s) hipStreamWaitEvent(s, ctx->done_evt, 0);
+inline int DevBuf::grow(dctae_ctx* ctx, size_t need, const char* what) {
+  if (need <= cap) return 0;
+  HIPCHK(ctx, hipDeviceSynchronize());   // the previous user may have run on another stream
+  release();
+  if (hipMalloc((void**)&p, need) != hipSuccess) {
+    p = nullptr;
+    return fail(ctx, DCTAE_ENOMEM, std::string(what) + " allocation of " + std::to_string(need) + " bytes failed");
+  }
+  cap = need;
+  return 0;
 }
 
-inline void mark_done(dctae_ctx* ctx, hipStream_t s) {
-  hipEventRecord(ctx->done_evt, s);
-  ctx->last_stream = s;
-  ctx->have_done = true;
-}
+// One call's use of the context's scratch and plan.  The constructor orders
+// the call's stream after the context's previous ordered call on another
+// stream (on the same stream it does nothing); the destructor records, on
+// every exit path, the event the next call waits for.  Declare it before the
+// call's Timers and its SideStream: their destructors (the timer's end event,
+// the side stream's join) then run before the record.
+class OrderedCall {
+ public:
+  dctae_ctx* const ctx;
+  const hipStream_t s;
+  OrderedCall(dctae_ctx* c, hipStream_t st) : ctx(c), s(st) {
+    if (ctx->have_done && ctx->last_stream != s) hipStreamWaitEvent(s, ctx->done_evt, 0);
+  }
+  ~OrderedCall() {
+    hipEventRecord(ctx->done_evt, s);
+    ctx->last_stream = s;
+    ctx->have_done = true;
+  }
+  OrderedCall(const OrderedCall&) = delete;
+  // *out = the scratch buffer `which`, grown to at least `bytes` (0: as it is)
+  template <class T>
+  int scratch(Scratch which, size_t bytes, T** out) {
+    uint8_t* p = nullptr;
+    const int rc = scratch_bytes(which, bytes, &p);
+    *out = reinterpret_cast<T*>(p);
+    return rc;
+  }
+  // *base = the device copy of pb (uploaded on s unless the plan buffer holds
+  // these bytes already: the same non-zero plan_id, or equal bytes)
+  int upload(const PlanBuf& pb, uint8_t** base, uint64_t plan_id = 0);
+
+ private:
+  int scratch_bytes(Scratch which, size_t bytes, uint8_t** out);
+  unsigned poisoned = 0;   // Options::ws_poison: the buffers this call has filled, one bit each
+};
 
 inline void ctx_gemm(const dctae_ctx* ctx, int nc, const GemmProblem* probs, const TileRef* tiles, int n_tiles,
                      hipStream_t s, int share = 0) {
@@ -173,13 +227,8 @@ inline void ctx_gemm(const dctae_ctx* ctx, int nc, const GemmProblem* probs, con
     launch_gemm(nc, probs, tiles, n_tiles, s, share);
 }
 
-// ---- dctae_api.hip ----
-int upload_plan(dctae_ctx* ctx, const PlanBuf& pb, hipStream_t s, uint64_t plan_id = 0);
-int ensure_ws(dctae_ctx* ctx, size_t ws_bytes, size_t stage_bytes);
-
 // ---- dctae_plan.hip ----
 int dct_matrix(dctae_ctx* ctx, int N, int rows, const float** out, int parity = -1);
-int proj_scratch(dctae_ctx* ctx, int N, int K);
 void attach_x3(const dctae_ctx* ctx, GemmProblem& g);
 int check_cfg(dctae_ctx* ctx, const dctae_fe_cfg* cfg);
 int check_lfq(dctae_ctx* ctx, const dctae_lfq* lfq, int PP);

@@ -39,11 +39,12 @@ static DecodeArgs decode_args(const dctae_ctx* ctx, const dctae_fe_cfg* cfg, con
 
 // decode of 512 x 512 images on the FFT path: token map -> column DCT-III
 // (tokens expanded in the kernel) -> U -> row DCT-III + IPT -> RGB
-static int decode_fft(dctae_ctx* ctx, const dctae_fe_cfg* cfg, std::vector<ImgDesc>& D, const FftPlan& fpl,
+static int decode_fft(OrderedCall& oc, const dctae_fe_cfg* cfg, std::vector<ImgDesc>& D, const FftPlan& fpl,
                       int32_t n_rows, const int32_t* img_lut, int32_t lut_w, const int64_t* ids,
                       const uint8_t* key_pad, const int64_t* pos, const int64_t* ch, const dctae_norm* norm,
-                      const dctae_lfq* lfq, const int64_t* codes, const float* patches, float* rgb, hipStream_t s,
-                      bool normed) {
+                      const dctae_lfq* lfq, const int64_t* codes, const float* patches, float* rgb, bool normed) {
+  dctae_ctx* ctx = oc.ctx;
+  const hipStream_t s = oc.s;
   const int n_img = (int)D.size();
   const int S = cfg->max_seq_len;
   int64_t wsf = 0;
@@ -58,16 +59,16 @@ static int decode_fft(dctae_ctx* ctx, const dctae_fe_cfg* cfg, std::vector<ImgDe
   const int64_t map_n = (int64_t)n_img * 3 * cfg->max_patch_h * cfg->max_patch_w;
   wsf += map_n;
   int rc;
-  if ((rc = ensure_ws(ctx, (size_t)wsf * 4, 256))) return rc;
+  float* ws;
+  if ((rc = oc.scratch(kWs, (size_t)wsf * 4, &ws))) return rc;
   PlanBuf pb;
   const size_t d_off = pb.add(D.data(), D.size());
   const size_t rb_off = pb.add(rb.data(), rb.size());
   const size_t lut_off = pb.add(img_lut, (size_t)n_rows * lut_w);
-  order_after_previous(ctx, s);
-  if ((rc = upload_plan(ctx, pb, s))) return rc;
-  uint8_t* pd = ctx->plan_dev;
+  uint8_t* pd;
+  if ((rc = oc.upload(pb, &pd))) return rc;
   const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
-  int32_t* map = (int32_t*)(ctx->ws + map_off);
+  int32_t* map = (int32_t*)(ws + map_off);
   HIPCHK(ctx, hipMemsetAsync(map, 0xFF, (size_t)map_n * 4, s));
   const DecodeArgs a = decode_args(ctx, cfg, ids, key_pad, pos, ch, norm, lfq, codes, patches,
                                    (const int32_t*)(pd + lut_off), lut_w, normed);
@@ -84,19 +85,18 @@ static int decode_fft(dctae_ctx* ctx, const dctae_fe_cfg* cfg, std::vector<ImgDe
   {
     Timer t(ctx, s, "idct_cols");
     if (band)
-      launch_idct_cols512b(dd, n_img, ctx->ws, map, tw, pre, a, s);
+      launch_idct_cols512b(dd, n_img, ws, map, tw, pre, a, s);
     else
-      launch_idct_cols512(dd, n_img, D[0].qw, ctx->ws, map, tw, pre, a, s);
+      launch_idct_cols512(dd, n_img, D[0].qw, ws, map, tw, pre, a, s);
   }
   {
     Timer t(ctx, s, "idct_rows");
     if (rows512)
-      launch_idct_rows512(band, dd, (const int2*)(pd + rb_off), (int)rb.size(), ctx->ws, rgb, tw, pre, ctx->cm, s);
+      launch_idct_rows512(band, dd, (const int2*)(pd + rb_off), (int)rb.size(), ws, rgb, tw, pre, ctx->cm, s);
     else
-      launch_idct_rows_spec(1, dd, (const int2*)(pd + rb_off), (int)rb.size(), ctx->ws, rgb, tw, pre, ctx->cm, s);
+      launch_idct_rows_spec(1, dd, (const int2*)(pd + rb_off), (int)rb.size(), ws, rgb, tw, pre, ctx->cm, s);
   }
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -163,24 +163,22 @@ static int decode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, 
     fftdec = D[i].H == 512 && D[i].W == 512 && D[i].qh <= 32 && D[i].qw == D[0].qw;
   FftPlan fpl{};
   if (fftdec) fftdec = fft_plan_for(ctx, 512, P, &fpl) == 0 && fpl.spec == 1;
+  OrderedCall oc(ctx, s);
   if (fftdec)
-    return decode_fft(ctx, cfg, D, fpl, n_rows, img_lut, lut_w, ids, key_pad, pos, ch, norm, lfq, codes, patches,
-                      rgb, s, normed);
+    return decode_fft(oc, cfg, D, fpl, n_rows, img_lut, lut_w, ids, key_pad, pos, ch, norm, lfq, codes, patches, rgb,
+                      normed);
   if (normed && n_rows > 0) {
-    // other geometries: the inverse over every packed token into the staging
-    // buffer (after the previous call, which may still read it), then as patches
+    // other geometries: the inverse over every packed token into the staging buffer, then as patches
     const int64_t n_tok = (int64_t)n_rows * S;
-    if ((rc = ensure_ws(ctx, 0, (size_t)n_tok * PP * 4))) return rc;
-    order_after_previous(ctx, s);
-    float* inv = reinterpret_cast<float*>(ctx->stage);
-    {
-      Timer t(ctx, s, "norm_inverse");
-      launch_norm(patches, ch, pos, n_tok, PP, cfg->max_patch_h, cfg->max_patch_w, norm->median_dev, norm->b_dev,
-                  norm->eps, norm->min_val, norm->max_val, 1, inv, ctx->err_dev, s);
-    }
+    float* inv;
+    if ((rc = oc.scratch(kStage, (size_t)n_tok * PP * 4, &inv))) return rc;
+    Timer t(ctx, s, "norm_inverse");
+    launch_norm(patches, ch, pos, n_tok, PP, cfg->max_patch_h, cfg->max_patch_w, norm->median_dev, norm->b_dev,
+                norm->eps, norm->min_val, norm->max_val, 1, inv, ctx->err_dev, s);
     patches = inv;
   }
-  if ((rc = ensure_ws(ctx, (size_t)(gmap_off + gmap_n) * 4, 256))) return rc;
+  float* ws;
+  if ((rc = oc.scratch(kWs, (size_t)(gmap_off + gmap_n) * 4, &ws))) return rc;
   const int rows_cap = P * std::max(cfg->max_patch_h, cfg->max_patch_w);
   std::vector<GemmProblem> probs;
   std::vector<TileRef> t1, t2;
@@ -189,7 +187,6 @@ static int decode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, 
     const float *CW, *CH;
     if ((rc = dct_matrix(ctx, d.W, std::min(d.W, rows_cap), &CW))) return rc;
     if ((rc = dct_matrix(ctx, d.H, std::min(d.H, rows_cap), &CH))) return rc;
-    float* ws = ctx->ws;
     // U[c][y][kx] = sum_ky CH[ky][y] * Ysp[c][ky][kx]
     GemmProblem g1 = gemm(CH, 0, 1, d.H, ws + d.ws_y, (int64_t)d.Kh * d.Kw, 1, d.Kw, ws + d.ws_t,
                           (int64_t)d.H * d.Kw, d.Kw, 1, d.H, d.Kw, d.Kh, 3);
@@ -214,15 +211,14 @@ static int decode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, 
   size_t t1_off = pb.add(t1.data(), t1.size());
   size_t t2_off = pb.add(t2.data(), t2.size());
   size_t lut_off = pb.add(img_lut, (size_t)n_rows * lut_w);
-  order_after_previous(ctx, s);
-  if ((rc = upload_plan(ctx, pb, s))) return rc;
-  uint8_t* pd = ctx->plan_dev;
+  uint8_t* pd;
+  if ((rc = oc.upload(pb, &pd))) return rc;
   const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
-  HIPCHK(ctx, hipMemsetAsync(ctx->ws, 0, (size_t)wsf * 4, s));
+  HIPCHK(ctx, hipMemsetAsync(ws, 0, (size_t)wsf * 4, s));
   // PatchNorm-space patches were inverted into the staging buffer above: plain patches here
   const DecodeArgs a = decode_args(ctx, cfg, ids, key_pad, pos, ch, norm, lfq, codes, patches,
                                    (const int32_t*)(pd + lut_off), lut_w, false);
-  int32_t* gmap = (int32_t*)(ctx->ws + gmap_off);
+  int32_t* gmap = (int32_t*)(ws + gmap_off);
   HIPCHK(ctx, hipMemsetAsync(gmap, 0xFF, (size_t)gmap_n * 4, s));
   {
     Timer t(ctx, s, "dec_map");
@@ -230,7 +226,7 @@ static int decode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, 
   }
   {
     Timer t(ctx, s, "scatter_tokens");
-    launch_scatter_tokens((int64_t)n_rows * S, dd, ctx->ws, a, gmap, s);
+    launch_scatter_tokens((int64_t)n_rows * S, dd, ws, a, gmap, s);
   }
   {
     Timer t(ctx, s, "idct_cols");
@@ -242,10 +238,9 @@ static int decode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, 
   }
   {
     Timer t(ctx, s, "ipt_to_rgb");
-    launch_ipt_to_rgb(dd, n_img, max_hw, ctx->ws, rgb, ctx->cm, s);
+    launch_ipt_to_rgb(dd, n_img, max_hw, ws, rgb, ctx->cm, s);
   }
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 

@@ -293,22 +293,20 @@ int dctae_pixel_loss_forward(dctae_ctx* ctx, int32_t n_img, const int32_t* out_h
   // at least four float4 per thread and block; at most kLossBlocks blocks per image
   const int gx = (int)std::min<int64_t>(kLossBlocks, (max_n + 16 * kThreads - 1) / (16 * kThreads));
   int rc;
-  if ((rc = ensure_ws(ctx, std::max<size_t>((size_t)n_img * gx * sizeof(double), 512), 256))) return rc;
+  OrderedCall oc(ctx, s);
+  double* part;
+  if ((rc = oc.scratch(kWs, std::max<size_t>((size_t)n_img * gx * sizeof(double), 512), &part))) return rc;
   PlanBuf pb;
   const size_t d_off = pb.add(D.data(), D.size());
-  order_after_previous(ctx, s);
-  if ((rc = upload_plan(ctx, pb, s))) return rc;
-  const PixImg* dd = (const PixImg*)(ctx->plan_dev + d_off);
-  double* part = reinterpret_cast<double*>(ctx->ws);
-  {
-    Timer t(ctx, s, "pixel_loss_forward");
-    if (n_img > 0)
-      k_pixel_loss_fwd<<<dim3(gx, n_img), kThreads, 0, s>>>(dd, rgb_hat_dev, rgb_dev,
-                                                            aligned16({rgb_hat_dev, rgb_dev}) ? 1 : 0, part);
-    k_pixel_loss_finish<<<1, kThreads, 0, s>>>(dd, part, gx, n_img, scalars_dev);
-  }
+  uint8_t* pd;
+  if ((rc = oc.upload(pb, &pd))) return rc;
+  const PixImg* dd = (const PixImg*)(pd + d_off);
+  Timer t(ctx, s, "pixel_loss_forward");
+  if (n_img > 0)
+    k_pixel_loss_fwd<<<dim3(gx, n_img), kThreads, 0, s>>>(dd, rgb_hat_dev, rgb_dev,
+                                                          aligned16({rgb_hat_dev, rgb_dev}) ? 1 : 0, part);
+  k_pixel_loss_finish<<<1, kThreads, 0, s>>>(dd, part, gx, n_img, scalars_dev);
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -370,7 +368,9 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
   const int64_t gmap_off = wsf;
   const int64_t gmap_n = (int64_t)n_img * 3 * cfg->max_patch_h * cfg->max_patch_w;
   const int64_t dc_off = (gmap_off + gmap_n + 63) & ~63ll;   // the images' DC coefficients, 3 floats each
-  if ((rc = ensure_ws(ctx, std::max<size_t>((size_t)(dc_off + 3ll * n_img) * 4, 512), 256))) return rc;
+  OrderedCall oc(ctx, s);
+  float* ws;
+  if ((rc = oc.scratch(kWs, std::max<size_t>((size_t)(dc_off + 3ll * n_img) * 4, 512), &ws))) return rc;
   const int rows_cap = P * std::max(cfg->max_patch_h, cfg->max_patch_w);
   std::vector<GemmProblem> probs;
   std::vector<TileRef> t1, t2, t3, t4;
@@ -379,7 +379,6 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
     const float *CW, *CH;
     if ((rc = dct_matrix(ctx, d.W, std::min(d.W, rows_cap), &CW))) return rc;
     if ((rc = dct_matrix(ctx, d.H, std::min(d.H, rows_cap), &CH))) return rc;
-    float* ws = ctx->ws;
     // the decode's pair: U[c][y][kx] = sum_ky CH[ky][y] Y[c][ky][kx];  ipt[c][y][x] = sum_kx U[c][y][kx] CW[kx][x]
     GemmProblem g1 = gemm(CH, 0, 1, d.H, ws + d.ws_y, (int64_t)d.Kh * d.Kw, 1, d.Kw, ws + d.ws_t,
                           (int64_t)d.H * d.Kw, d.Kw, 1, d.H, d.Kw, d.Kh, 3);
@@ -413,9 +412,8 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
   const size_t t3_off = pb.add(t3.data(), t3.size());
   const size_t t4_off = pb.add(t4.data(), t4.size());
   const size_t lut_off = pb.add(img_lut, (size_t)n_rows * lut_w);
-  order_after_previous(ctx, s);
-  if ((rc = upload_plan(ctx, pb, s))) return rc;
-  uint8_t* pd = ctx->plan_dev;
+  uint8_t* pd;
+  if ((rc = oc.upload(pb, &pd))) return rc;
   const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
   const GemmProblem* gp = (const GemmProblem*)(pd + g_off);
   DecodeArgs a{};
@@ -431,9 +429,9 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
   a.maxph = cfg->max_patch_h;
   a.maxpw = cfg->max_patch_w;
   a.err = ctx->err_dev;
-  int32_t* gmap = (int32_t*)(ctx->ws + gmap_off);
+  int32_t* gmap = (int32_t*)(ws + gmap_off);
   if (n_img > 0) {
-    HIPCHK(ctx, hipMemsetAsync(ctx->ws, 0, (size_t)y_floats * 4, s));
+    HIPCHK(ctx, hipMemsetAsync(ws, 0, (size_t)y_floats * 4, s));
     HIPCHK(ctx, hipMemsetAsync(gmap, 0xFF, (size_t)gmap_n * 4, s));
   }
   {
@@ -443,8 +441,8 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
   if (n_img > 0) {
     {
       Timer t(ctx, s, "bwd_recompute_ipt");
-      launch_scatter_tokens(n_tok, dd, ctx->ws, a, gmap, s);
-      k_take_dc<<<n_img, 64, 0, s>>>(dd, ctx->ws, ctx->ws + dc_off);
+      launch_scatter_tokens(n_tok, dd, ws, a, gmap, s);
+      k_take_dc<<<n_img, 64, 0, s>>>(dd, ws, ws + dc_off);
       ctx_gemm(ctx, 3, gp, (const TileRef*)(pd + t1_off), (int)t1.size(), s, 2);
       ctx_gemm(ctx, 3, gp, (const TileRef*)(pd + t2_off), (int)t2.size(), s, 1);
     }
@@ -452,7 +450,7 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
       Timer t(ctx, s, "color_bwd");
       const int gx = (int)std::min<int64_t>((max_hw + 4 * kThreads - 1) / (4 * kThreads), 256);
       const bool vb = grad_rgb ? aligned16({grad_rgb}) : aligned16({rgb_hat, rgb});
-      k_color_bwd<<<dim3(gx, n_img), kThreads, 0, s>>>(dd, ctx->ws, grad_rgb, rgb_hat, rgb, g, ctx->ws + dc_off, n_img,
+      k_color_bwd<<<dim3(gx, n_img), kThreads, 0, s>>>(dd, ws, grad_rgb, rgb_hat, rgb, g, ws + dc_off, n_img,
                                                        vb ? 1 : 0, ctx->cm);
     }
     {
@@ -470,12 +468,11 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
     const int64_t units = n_tok * (vec ? PP / 4 : PP);
     const int nb = (int)std::min<int64_t>((units + kThreads - 1) / kThreads, 16384);
     if (vec)
-      k_gather_tokens<4><<<nb, kThreads, 0, s>>>(units, dd, ctx->ws, a, gmap, dpatches);
+      k_gather_tokens<4><<<nb, kThreads, 0, s>>>(units, dd, ws, a, gmap, dpatches);
     else
-      k_gather_tokens<1><<<nb, kThreads, 0, s>>>(units, dd, ctx->ws, a, gmap, dpatches);
+      k_gather_tokens<1><<<nb, kThreads, 0, s>>>(units, dd, ws, a, gmap, dpatches);
   }
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 

@@ -45,6 +45,7 @@ struct EncPlan {
   int64_t n_tok = 0;
   size_t rowlen_off = 0, plans_off = 0;
   size_t ws_need = 0, st_need = 0;
+  float* ws = nullptr;   // the workspace its GEMM problems point into: the plan drops when the workspace moves
   int ncb = 0;
   bool any_pad = true;   // some packed row shorter than max_seq_len
   bool uniform = false;  // every image of the call has the same (H, W)
@@ -55,9 +56,10 @@ struct EncPlan {
 // scores_dev at tok_off).  Per image the row DCT (length W) and the column
 // DCT (length H) each run on the FFT kernels when the length has a plan, else
 // on the MFMA GEMM; the intermediate T[c][y][kx] (3, H, Kw) is shared.
-static int build_encode_plan(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
+static int build_encode_plan(OrderedCall& oc, const dctae_fe_cfg* cfg, const dctae_images* imgs,
                              const dctae_packing* pack, bool full, int ncb, bool want_raw, bool want_norm,
                              const int64_t* tok_off_user, EncPlan& E) {
+  dctae_ctx* ctx = oc.ctx;
   const int n = imgs->n_img;
   const int P = cfg->patch_size, PP = P * P, S = cfg->max_seq_len;
   int rc;
@@ -175,8 +177,12 @@ static int build_encode_plan(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dcta
     for (int i = 0; i < n; ++i) st += st_of(D[i]);
     E.st_need = (size_t)st + 4096;
   }
-  if ((rc = ensure_ws(ctx, std::max<size_t>(E.ws_need, 256), std::max<size_t>(E.st_need, 256)))) return rc;
-  float* ws = ctx->ws;
+  // both buffers are sized where the plan is built (token_sinks carves the staging)
+  uint8_t* st;
+  if ((rc = oc.scratch(kWs, std::max<size_t>(E.ws_need, 256), &E.ws)) ||
+      (rc = oc.scratch(kStage, std::max<size_t>(E.st_need, 256), &st)))
+    return rc;
+  float* ws = E.ws;
   for (auto& j : E.jobs) {
     j.desc_off = E.pb.add(D.data() + j.i0, j.i1 - j.i0);
     const size_t p0 = probs.size();
@@ -441,7 +447,7 @@ int EncCall::check(dctae_ctx* ctx) {
 }
 
 // plan cache key: every input that shapes the launch sequence (the workspace
-// pointer is compared beside it: dctae_ctx::enc_ws)
+// pointer is compared beside it: EncPlan::ws)
 std::vector<int64_t> EncCall::plan_key(const Options& opt) const {
   const int n = imgs->n_img;
   std::vector<int64_t> key;
@@ -467,12 +473,16 @@ std::vector<int64_t> EncCall::plan_key(const Options& opt) const {
 }
 
 // the call's plan: the cached one, or a new one that replaces it
-static int encode_plan(dctae_ctx* ctx, const EncCall& c, EncPlan** out) {
+static int encode_plan(OrderedCall& oc, const EncCall& c, EncPlan** out) {
+  dctae_ctx* ctx = oc.ctx;
   std::vector<int64_t> key = c.plan_key(ctx->opt);
-  if (!ctx->enc_plan || ctx->enc_ws != ctx->ws || key != ctx->enc_key) {
+  float* ws;   // as it is now: another call may have moved it since the plan was built
+  int rc = oc.scratch(kWs, 0, &ws);
+  if (rc) return rc;
+  if (!ctx->enc_plan || ctx->enc_plan->ws != ws || key != ctx->enc_key) {
     EncPlan* E = new EncPlan();
     E->id = ++ctx->plan_counter;
-    int rc = build_encode_plan(ctx, c.cfg, c.imgs, c.pack, c.full, c.ncb, c.want_raw, c.want_norm, c.tok_off_user, *E);
+    rc = build_encode_plan(oc, c.cfg, c.imgs, c.pack, c.full, c.ncb, c.want_raw, c.want_norm, c.tok_off_user, *E);
     if (rc) {
       delete E;
       return rc;
@@ -480,7 +490,6 @@ static int encode_plan(dctae_ctx* ctx, const EncCall& c, EncPlan** out) {
     delete ctx->enc_plan;
     ctx->enc_plan = E;
     ctx->enc_key = std::move(key);
-    ctx->enc_ws = ctx->ws;   // the plan holds workspace addresses, and ensure_ws may have moved it
   }
   *out = ctx->enc_plan;
   return 0;
@@ -505,16 +514,17 @@ static PackSinks pack_sinks(const dctae_packed_out* out) {
 }
 
 // token staging for the whole call (flat token order, global offsets)
-static TokenSinks token_sinks(const dctae_ctx* ctx, const EncCall& c, const EncPlan& E) {
-  TokenSinks sk{};
+static int token_sinks(OrderedCall& oc, const EncCall& c, const EncPlan& E, TokenSinks& sk) {
+  sk = TokenSinks{};
   if (!c.full) {
     sk.scores = c.scores_dev;
     sk.raw = c.tokens_dev;
-    return sk;
+    return 0;
   }
   const int PP = c.cfg->patch_size * c.cfg->patch_size;
   const int64_t nt = E.n_tok;
-  uint8_t* st = ctx->stage;
+  uint8_t* st;
+  if (int rc = oc.scratch(kStage, std::max<size_t>(E.st_need, 256), &st)) return rc;
   sk.scores = (float*)st;
   st += ((nt * 4 + 255) & ~255ll);
   if (c.ncb) {
@@ -529,13 +539,13 @@ static TokenSinks token_sinks(const dctae_ctx* ctx, const EncCall& c, const EncP
     sk.raw = (float*)st;
     st += nt * 4 * PP;
   }
-  return sk;
+  return 0;
 }
 
 // The context's side stream for the length of one call.  fork(s) lets the side
 // stream start after what `s` holds so far; once forked, `s` waits for the side
-// stream at join() and on every exit (error returns included), so the next
-// call's order_after_previous covers it before the workspace is reused.
+// stream at join() and on every exit (error returns included), so the call's
+// OrderedCall, declared before it, records the side stream's work too.
 struct SideStream {
   dctae_ctx* ctx;
   hipStream_t s = nullptr;
@@ -591,7 +601,7 @@ struct EncLaunch {
   // row half of a chunk job on a stream
   void do_rows(const ChunkJob& j, hipStream_t st) const {
     const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
-    uint32_t* amax = reinterpret_cast<uint32_t*>(ctx->ws + j.amax_off);
+    uint32_t* amax = reinterpret_cast<uint32_t*>(E.ws + j.amax_off);
     if (j.h2 || j.any_fused) hipMemsetAsync(amax, 0, 12 * (size_t)(j.i1 - j.i0) + 36, st);   // errors surface at hipGetLastError
     if (j.any_fused) {
       int* flags = reinterpret_cast<int*>(amax + 2 * (j.i1 - j.i0));
@@ -607,7 +617,7 @@ struct EncLaunch {
     if (j.any_gemm_rows) {
       {
         Timer t(ctx, st, "rgb_to_ipt");
-        launch_rgb_to_ipt(dd, (const int2*)(pd + j.ipt_off), j.n_ipt, imgs->rgb_dev, ctx->ws, ctx->cm,
+        launch_rgb_to_ipt(dd, (const int2*)(pd + j.ipt_off), j.n_ipt, imgs->rgb_dev, E.ws, ctx->cm,
                           j.h2 ? amax : nullptr, st);
       }
       Timer t(ctx, st, "gemm_rows");
@@ -616,22 +626,22 @@ struct EncLaunch {
     for (int l = 0; l < 4; ++l)
       if (j.n_br[l]) {
         Timer t(ctx, st, "bs_rows");
-        launch_bs_rows(kBsL[l], dd, plans_d, (const int2*)(pd + j.br_off[l]), j.n_br[l], imgs->rgb_dev, ctx->ws,
+        launch_bs_rows(kBsL[l], dd, plans_d, (const int2*)(pd + j.br_off[l]), j.n_br[l], imgs->rgb_dev, E.ws,
                        ctx->fft_tab, ctx->cm, st, ctx->opt.bs_ablate);
       }
     if (j.n_fr[0]) {
       Timer t(ctx, st, "fft_rows");
-      launch_fft_rows(dd, plans_d, (const int2*)(pd + j.fr_off[0]), j.n_fr[0], j.lds_rows, imgs->rgb_dev, ctx->ws,
+      launch_fft_rows(dd, plans_d, (const int2*)(pd + j.fr_off[0]), j.n_fr[0], j.lds_rows, imgs->rgb_dev, E.ws,
                       ctx->fft_tab, ctx->cm, st);
     }
     for (int v = 1; v < kVariants; ++v)
       if (j.n_fr[v]) {
         Timer t(ctx, st, "fft_rows");
         if (v == 1 && ctx->opt.rows_kernel == 4 && cfg->max_patch_w == 32)
-          launch_rows512(dd, (const int2*)(pd + j.fr_off[v]), j.n_fr[v], imgs->rgb_dev, ctx->ws,
+          launch_rows512(dd, (const int2*)(pd + j.fr_off[v]), j.n_fr[v], imgs->rgb_dev, E.ws,
                          ctx->fft_tab + j.tw_off[v], ctx->fft_tab + j.post_off_r[v], ctx->cm, st);
         else
-          launch_fft_rows_spec(v, dd, (const int2*)(pd + j.fr_off[v]), j.n_fr[v], imgs->rgb_dev, ctx->ws,
+          launch_fft_rows_spec(v, dd, (const int2*)(pd + j.fr_off[v]), j.n_fr[v], imgs->rgb_dev, E.ws,
                                ctx->fft_tab + j.tw_off[v], ctx->fft_tab + j.post_off_r[v], ctx->cm, st);
       }
   }
@@ -643,8 +653,8 @@ struct EncLaunch {
     if (j.any_gemm_cols) {
       if (j.fold_t) {
         Timer t(ctx, st, "fold_t");
-        launch_fold_t(dd, (const int32_t*)(pd + j.fold_off), j.n_fold, j.fold_max_hw, ctx->ws,
-                      j.h2 ? reinterpret_cast<uint32_t*>(ctx->ws + j.amax_off) : nullptr, st);
+        launch_fold_t(dd, (const int32_t*)(pd + j.fold_off), j.n_fold, j.fold_max_hw, E.ws,
+                      j.h2 ? reinterpret_cast<uint32_t*>(E.ws + j.amax_off) : nullptr, st);
       }
       Timer t(ctx, st, "gemm_cols");
       gemm(j, j.cols_t_off, j.n_cols_tiles, st, 2);
@@ -652,27 +662,27 @@ struct EncLaunch {
     for (int l = 0; l < 4; ++l)
       if (j.n_bc[l]) {
         Timer t(ctx, st, "bs_cols");
-        launch_bs_cols(kBsL[l], dd, plans_d, (const int4*)(pd + j.bc_off[l]), j.n_bc[l], ctx->ws, ctx->fft_tab, st,
+        launch_bs_cols(kBsL[l], dd, plans_d, (const int4*)(pd + j.bc_off[l]), j.n_bc[l], E.ws, ctx->fft_tab, st,
                        ctx->opt.bs_ablate);
       }
     if (j.any_gemm_cols || j.any_bs_cols) {
       Timer t(ctx, st, "tile_epilogue");
-      launch_tile_epilogue(dd, nj, j.max_T, ctx->ws, epj, skc, st, (const int2*)(pd + j.epi_off), j.n_epi);
+      launch_tile_epilogue(dd, nj, j.max_T, E.ws, epj, skc, st, (const int2*)(pd + j.epi_off), j.n_epi);
     }
     if (j.n_fc[0]) {
       Timer t(ctx, st, "fft_cols");
-      launch_fft_cols(dd, plans_d, (const int4*)(pd + j.fc_off[0]), j.n_fc[0], j.lds_cols, ctx->ws, ctx->fft_tab,
+      launch_fft_cols(dd, plans_d, (const int4*)(pd + j.fc_off[0]), j.n_fc[0], j.lds_cols, E.ws, ctx->fft_tab,
                       epj, skc, st);
     }
     if (j.n_pb) {
       Timer t(ctx, st, "fft_cols");
-      launch_cols512b(dd, (const int*)(pd + j.pb_off), j.n_pb, ctx->ws, ctx->fft_tab + j.tw_off_c[1],
+      launch_cols512b(dd, (const int*)(pd + j.pb_off), j.n_pb, E.ws, ctx->fft_tab + j.tw_off_c[1],
                       ctx->fft_tab + j.post_off_c[1], epj, skc, st, ctx->opt.cols_wide != 0);
     }
     for (int v = 1; v < kVariants; ++v)
       if (j.n_fc[v]) {
         Timer t(ctx, st, "fft_cols");
-        launch_fft_cols_spec(v, dd, (const int4*)(pd + j.fc_off[v]), j.n_fc[v], ctx->ws, ctx->fft_tab + j.tw_off_c[v],
+        launch_fft_cols_spec(v, dd, (const int4*)(pd + j.fc_off[v]), j.n_fc[v], E.ws, ctx->fft_tab + j.tw_off_c[v],
                              ctx->fft_tab + j.post_off_c[v], epj, skc, st,
                              v == 1 && j.n_pc ? (const int*)(pd + j.pc_off) : nullptr, v == 1 ? j.n_pc : 0, j.pc_qw);
       }
@@ -710,12 +720,12 @@ struct EncLaunch {
     const int4* cl = (const int4*)(pd + j.fc_off[hv]);
     auto rows = [&](int a, int m, hipStream_t st) {
       Timer t(ctx, st, "fft_rows");
-      launch_fft_rows_spec(hv, dd, rl + (size_t)a * rpi, m * rpi, imgs->rgb_dev, ctx->ws, ctx->fft_tab + j.tw_off[hv],
+      launch_fft_rows_spec(hv, dd, rl + (size_t)a * rpi, m * rpi, imgs->rgb_dev, E.ws, ctx->fft_tab + j.tw_off[hv],
                            ctx->fft_tab + j.post_off_r[hv], ctx->cm, st);
     };
     auto cols = [&](int a, int m, hipStream_t st) {
       Timer t(ctx, st, "fft_cols");
-      launch_fft_cols_spec(hv, dd, cl + (size_t)a * cpi, m * cpi, ctx->ws, ctx->fft_tab + j.tw_off_c[hv],
+      launch_fft_cols_spec(hv, dd, cl + (size_t)a * cpi, m * cpi, E.ws, ctx->fft_tab + j.tw_off_c[hv],
                            ctx->fft_tab + j.post_off_c[hv], epj, skc, st, nullptr, 0, 0);
     };
     rows(0, h, s);
@@ -740,14 +750,14 @@ struct EncLaunch {
     const int h = j.n_pb / 2;
     {
       Timer t(ctx, s, "fft_cols");
-      launch_cols512b(dd, list, h, ctx->ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1], epj, skc, s,
+      launch_cols512b(dd, list, h, E.ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1], epj, skc, s,
                       ctx->opt.cols_wide != 0);
     }
     if (int rc = side.fork(s)) return rc;
     sort_pack(0, h, ctx->side);
     {
       Timer t(ctx, s, "fft_cols");
-      launch_cols512b(dd, list + h, j.n_pb - h, ctx->ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1],
+      launch_cols512b(dd, list + h, j.n_pb - h, E.ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1],
                       epj, skc, s, ctx->opt.cols_wide != 0);
     }
     *sorted0 = h;
@@ -769,12 +779,12 @@ struct EncLaunch {
     const int* cl = (const int*)(pd + j.pb_off);
     auto rows = [&](int a, int m, hipStream_t st) {
       Timer t(ctx, st, "fft_rows");
-      launch_rows512(dd, rl + (size_t)a * rpi, m * rpi, imgs->rgb_dev, ctx->ws, ctx->fft_tab + j.tw_off[1],
+      launch_rows512(dd, rl + (size_t)a * rpi, m * rpi, imgs->rgb_dev, E.ws, ctx->fft_tab + j.tw_off[1],
                      ctx->fft_tab + j.post_off_r[1], ctx->cm, st);
     };
     auto cols = [&](int a, int m, hipStream_t st) {
       Timer t(ctx, st, "fft_cols");
-      launch_cols512b(dd, cl + a, m, ctx->ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1], epj, skc,
+      launch_cols512b(dd, cl + a, m, E.ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1], epj, skc,
                       st, false);
     };
     const int64_t gate = ctx->opt.gate;
@@ -809,14 +819,14 @@ static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_imag
   int rc = c.check(ctx);
   if (rc) return rc;
   const bool full = c.full;
+  OrderedCall oc(ctx, s);   // before the plan: building it sizes the workspace
   EncPlan* plan;
-  if ((rc = encode_plan(ctx, c, &plan))) return rc;
+  if ((rc = encode_plan(oc, c, &plan))) return rc;
   const EncPlan& E = *plan;
   if (proj_w && E.any_pad)
     return fail(ctx, DCTAE_EUNSUP, "fused LFQ projections need rows without padding (the pad token's codes)");
-  order_after_previous(ctx, s);
-  if ((rc = upload_plan(ctx, E.pb, s, E.id))) return rc;
-  uint8_t* pd = ctx->plan_dev;
+  uint8_t* pd;
+  if ((rc = oc.upload(E.pb, &pd, E.id))) return rc;
 
   EncParams ep = enc_params(cfg, norm, c.want_codes && !proj_w ? lfq : nullptr);
   if (norm && !c.want_norm) ep.thr = norm->thr_dev;
@@ -842,7 +852,7 @@ static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_imag
       launch_pad_fill((const int32_t*)(pd + E.rowlen_off), pack->n_rows, ep, out->key_pad_dev, L.ps, s);
     }
   }
-  L.sk = token_sinks(ctx, c, E);
+  if ((rc = token_sinks(oc, c, E, L.sk))) return rc;
   L.skc = L.sk;   // the column kernels' sinks (codes come from the projection kernel)
   if (proj_w) L.skc.codes = nullptr;
 
@@ -876,12 +886,13 @@ static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_imag
   if (proj_w && E.n_tok > 0) {
     Timer t(ctx, s, "lfq_project_in");
     const int PP = cfg->patch_size * cfg->patch_size;
-    if ((rc = proj_scratch(ctx, lfq->codebook_dim * lfq->num_codebooks, PP))) return rc;
+    uint16_t* wsp;
+    if ((rc = oc.scratch(kProj, lfq_proj_scratch_bytes(lfq->codebook_dim * lfq->num_codebooks, PP), &wsp))) return rc;
     // the staged tokens are PatchNorm outputs, clamped to [min_val, max_val]
     // (patchnorm.py:163): the fp16 projection's operand bound
     const float xb = ctx->opt.gemm_h2 ? std::max(std::fabs(norm->min_val), std::fabs(norm->max_val)) : 0.0f;
     launch_lfq_project_in16(L.sk.norm, E.n_tok, PP, proj_w, proj_b, lfq->codebook_dim, lfq->num_codebooks, L.sk.codes,
-                            ctx->proj_ws, s, xb, ctx->opt.lfq_ws != 0);
+                            wsp, s, xb, ctx->opt.lfq_ws != 0);
   }
   if (full && E.n_img > sorted0) {
     Timer t(ctx, s, "sort_pack");
@@ -889,7 +900,6 @@ static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_imag
   }
   side.join();   // every output complete on the caller's stream
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -942,9 +952,10 @@ int dctae_dct2(dctae_ctx* ctx, const float* x, int32_t n_img, int32_t H, int32_t
   const float *CW, *CH;
   if ((rc = dct_matrix(ctx, W, W, &CW)) || (rc = dct_matrix(ctx, H, H, &CH))) return rc;
   // workspace: IPT (forward with colour) and the intermediate U / T, per image
-  if ((rc = ensure_ws(ctx, (size_t)2 * plane * n_img * 4, 256))) return rc;
-  float* a = ctx->ws;                        // forward: IPT input; inverse: IPT output
-  float* u = ctx->ws + plane * n_img;        // intermediate
+  OrderedCall oc(ctx, s);
+  float* a;                                  // forward: IPT input; inverse: IPT output
+  if ((rc = oc.scratch(kWs, (size_t)2 * plane * n_img * 4, &a))) return rc;
+  float* u = a + plane * n_img;              // intermediate
   std::vector<GemmProblem> probs;
   std::vector<TileRef> t1, t2;
   for (int i = 0; i < n_img; ++i) {
@@ -973,9 +984,8 @@ int dctae_dct2(dctae_ctx* ctx, const float* x, int32_t n_img, int32_t H, int32_t
   const size_t g_off = pb.add(probs.data(), probs.size());
   const size_t t1_off = pb.add(t1.data(), t1.size());
   const size_t t2_off = pb.add(t2.data(), t2.size());
-  order_after_previous(ctx, s);
-  if ((rc = upload_plan(ctx, pb, s))) return rc;
-  uint8_t* pd = ctx->plan_dev;
+  uint8_t* pd;
+  if ((rc = oc.upload(pb, &pd))) return rc;
   if (direction == 0 && color) {
     Timer t(ctx, s, "rgb_to_ipt");
     launch_color(x, a, hw, n_img, color >= 2 ? color : 0, ctx->cm, s);
@@ -992,7 +1002,6 @@ int dctae_dct2(dctae_ctx* ctx, const float* x, int32_t n_img, int32_t H, int32_t
     launch_color(a, y, hw, n_img, 1, ctx->cm, s);
   }
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 
@@ -1021,36 +1030,38 @@ int dctae_patch_spectrum(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const float* s
   const size_t y_bytes = (size_t)3 * d.Kh * d.Kw * 4;
   const size_t st_scores = ((size_t)d.T * 4 + 255) & ~size_t(255), st_raw = (size_t)d.T * PP * 4;
   const size_t st_ids = ((size_t)k * 8 + 255) & ~size_t(255);
-  if ((rc = ensure_ws(ctx, y_bytes, st_scores + st_raw + st_ids + 256))) return rc;
+  OrderedCall oc(ctx, s);
+  float* ws;
+  uint8_t *stage, *pd;
+  if ((rc = oc.scratch(kWs, y_bytes, &ws)) || (rc = oc.scratch(kStage, st_scores + st_raw + st_ids + 256, &stage)))
+    return rc;
   PlanBuf pb;
   const size_t d_off = pb.add(&d, 1);
-  order_after_previous(ctx, s);
-  if ((rc = upload_plan(ctx, pb, s))) return rc;
-  const ImgDesc* dd = (const ImgDesc*)(ctx->plan_dev + d_off);
+  if ((rc = oc.upload(pb, &pd))) return rc;
+  const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
   for (int c = 0; c < 3; ++c)   // kept corner (3, Kh, Kw) of the (3, H, W) spectrum
-    HIPCHK(ctx, hipMemcpy2DAsync(ctx->ws + (size_t)c * d.Kh * d.Kw, (size_t)d.Kw * 4, spec + (size_t)c * H * W,
+    HIPCHK(ctx, hipMemcpy2DAsync(ws + (size_t)c * d.Kh * d.Kw, (size_t)d.Kw * 4, spec + (size_t)c * H * W,
                                  (size_t)W * 4, (size_t)d.Kw * 4, d.Kh, hipMemcpyDeviceToDevice, s));
   EncParams ep = enc_params(cfg, nullptr, nullptr);
   ep.S = k;
   TokenSinks sk{};
-  sk.scores = (float*)ctx->stage;
-  sk.raw = (float*)(ctx->stage + st_scores);
+  sk.scores = (float*)stage;
+  sk.raw = (float*)(stage + st_scores);
   PackSinks ps{};
   ps.pos = positions;
   ps.ch = channels;
-  ps.ids = (int64_t*)(ctx->stage + st_scores + st_raw);
+  ps.ids = (int64_t*)(stage + st_scores + st_raw);
   ps.raw = patches;
   ps.scores = scores;
   {
     Timer t(ctx, s, "tile_epilogue");
-    launch_tile_epilogue(dd, 1, d.T, ctx->ws, ep, sk, s);
+    launch_tile_epilogue(dd, 1, d.T, ws, ep, sk, s);
   }
   {
     Timer t(ctx, s, "sort_pack");
     launch_sort_pack(dd, 1, next_pow2(d.T), ep, sk, ps, s, ctx->opt.sort_kernel, d.T);
   }
   HIPCHK(ctx, hipGetLastError());
-  mark_done(ctx, s);
   return 0;
 }
 

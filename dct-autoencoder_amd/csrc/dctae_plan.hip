@@ -48,20 +48,6 @@ int dct_matrix(dctae_ctx* ctx, int N, int rows, const float** out, int parity) {
   return 0;
 }
 
-// grow-only scratch for the LFQ projections' pre-split weight (N x K)
-int proj_scratch(dctae_ctx* ctx, int N, int K) {
-  const size_t need = lfq_proj_scratch_bytes(N, K);
-  if (need <= ctx->proj_bytes) return 0;
-  HIPCHK(ctx, hipDeviceSynchronize());
-  if (ctx->proj_ws) hipFree(ctx->proj_ws);
-  ctx->proj_ws = nullptr;
-  ctx->proj_bytes = 0;
-  if (hipMalloc((void**)&ctx->proj_ws, need) != hipSuccess)
-    return fail(ctx, DCTAE_ENOMEM, "LFQ projection scratch allocation failed");
-  ctx->proj_bytes = need;
-  return 0;
-}
-
 // point a GEMM's shared DCT-matrix operand at its pre-split planes (used by
 // k_gemm_x3 only): the operand must be a whole cached matrix read row-major
 // with k contiguous

@@ -3,7 +3,7 @@ context's scratch").  Run on an MI355X: pytest -m gpu tests/test_gpu_streams.py
 
 (a) Ordering harness.  A dctae_ctx owns device memory that successive calls
 reuse; a call on one stream must wait for the context's previous call on
-another (order_after_previous / mark_done, csrc/dctae_ctx.h).  For a pair
+another (the OrderedCall scope, csrc/dctae_ctx.h).  For a pair
 (first, second) of calls on one context the harness
 
   1. warms both (second, then first: the workspace, the plan buffer and the

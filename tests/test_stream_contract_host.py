@@ -5,10 +5,11 @@ Every entry point whose last argument is the stream is classified here by the
 context-owned device memory it touches and by how a call on one stream is kept
 apart from the context's previous call on another:
 
-  ORDERED    the call runs between order_after_previous and mark_done
-             (csrc/dctae_ctx.h): its stream waits for the context's previous
-             ordered call, and the next ordered call waits for it.  These are
-             the rows tests/test_gpu_streams.py parametrises over.
+  ORDERED    the call runs inside an OrderedCall scope (csrc/dctae_ctx.h), the
+             only way to the context's scratch: its stream waits for the
+             context's previous ordered call, and the next ordered call waits
+             for it.  These are the rows tests/test_gpu_streams.py
+             parametrises over.
   HOST_SYNC  ordered in the same way, and the call also waits on the host for
              its own stream before it returns, so the ordering harness (which
              needs the host to run ahead of a parked stream) cannot time it;
@@ -137,15 +138,19 @@ def test_rows_are_well_formed():
     assert len(HARNESS_ROWS) == 21
 
 
-def _bodies():
-    """name -> body text of every extern "C" function, helpers they call by name included once"""
-    src = {}
+def _sources(suffixes):
     d = os.path.join(ROOT, "dct-autoencoder_amd", "csrc")
-    for f in os.listdir(d):
-        if f.endswith(".hip"):
+    src = {}
+    for f in sorted(os.listdir(d)):
+        if f.endswith(suffixes):
             with open(os.path.join(d, f)) as fh:
                 src[f] = fh.read()
-    text = "\n".join(src.values())
+    return src
+
+
+def _bodies():
+    """name -> body text of every extern "C" function, helpers they call by name included once"""
+    text = "\n".join(_sources(".hip").values())
     funcs = {}
     for m in re.finditer(r"^(?:static\s+)?(?:int|void)\s+(?:dctae::)?(\w+)\s*\([^;{]*?\)\s*(?:const\s*)?\{", text,
                          flags=re.M | re.S):
@@ -165,32 +170,44 @@ def _closure(funcs, name, seen=None):
     seen.add(name)
     body = funcs[name]
     for callee in set(re.findall(r"\b(\w+)\s*\(", body)):
-        if callee in funcs and callee not in ("order_after_previous", "mark_done"):
+        if callee in funcs:
             body += _closure(funcs, callee, seen)
     return body
 
 
-SCRATCH = r"ensure_ws|ctx->ws\b|ctx->stage\b|stats_scratch|proj_scratch|vq_scratch|upload_plan|ctx->plan_dev|ctx->proj_ws|ctx->vq_ws|ctx->st_ws"
+# an OrderedCall's accessors (the scratch buffers, the plan) and its construction
+SCRATCH = r"\.scratch\(|\.upload\("
+SCOPE = r"\bOrderedCall\s+\w+\s*\("
 
 
 def test_sources_agree_with_the_table():
     """every entry point that reaches the context's scratch, directly or through
-    a helper, also reaches order_after_previous and mark_done, and is an
-    ORDERED row; every other row reaches no scratch"""
+    a helper, opens an OrderedCall, and is an ORDERED row; every other row
+    reaches no scratch"""
     funcs = _bodies()
     for k, (res, how, _) in TABLE.items():
         assert k in funcs, f"{k}: no definition found under csrc/"
         body = _closure(funcs, k)
         uses = re.search(SCRATCH, body) is not None
-        ordered = "order_after_previous(" in body and "mark_done(" in body
+        ordered = re.search(SCOPE, body) is not None
         if how == ORDERED:
             assert uses, f"{k}: classified as a scratch user, but its body reaches none"
-            assert ordered, f"{k}: uses the context's scratch without order_after_previous / mark_done"
+            assert ordered, f"{k}: uses the context's scratch without an OrderedCall"
         elif how == HOST_SYNC:
             assert ordered and "hipStreamSynchronize" in body, k
         else:
             assert not uses, f"{k}: reaches the context's scratch but is classified {how}"
         assert ("err_dev" in res) == ("err_dev" in body), f"{k}: the table and the source disagree on ctx->err_dev"
+
+
+def test_old_spellings_are_gone():
+    """the free functions and the raw members that OrderedCall replaced: the
+    buffers are private to the context now, so nothing may name them"""
+    old = r"\b(?:order_after_previous|mark_done|ensure_ws|upload_plan|proj_scratch|vq_scratch)\s*\(|" \
+          r"ctx->(?:ws|stage|st_ws|vq_ws|proj_ws|plan_dev)\b"
+    for f, text in _sources((".hip", ".h")).items():
+        m = re.search(old, text)
+        assert m is None, f"csrc/{f}: {m.group(0)!r} bypasses OrderedCall"
 
 
 def test_header_states_the_rule():
