@@ -104,10 +104,9 @@ def image_set(images: Sequence[torch.Tensor]) -> Tuple[Images, torch.device, lis
     hw = []
     for im in imgs:
         hw += [im.shape[1], im.shape[2]]
-    keep = [imgs, i64(offs), i32(hw)]
-    desc = Images(C.c_void_p(base), C.cast(keep[1], C.POINTER(C.c_int64)), C.cast(keep[2], C.POINTER(C.c_int32)),
-                  len(imgs))
-    return desc, dev, keep
+    offs, hw = i64(offs), i32(hw)
+    desc = Images(C.c_void_p(base), C.cast(offs, C.POINTER(C.c_int64)), C.cast(hw, C.POINTER(C.c_int32)), len(imgs))
+    return desc, dev, [imgs, offs, hw]
 
 
 def batch_image_set(x: torch.Tensor) -> Tuple[Images, torch.device, list]:
@@ -118,10 +117,9 @@ def batch_image_set(x: torch.Tensor) -> Tuple[Images, torch.device, list]:
     dev = _check_dev(x)
     B, c, H, W = x.shape
     per = c * H * W
-    keep = [x, i64([i * per for i in range(B)]), i32([H, W] * B)]
-    desc = Images(C.c_void_p(x.data_ptr()), C.cast(keep[1], C.POINTER(C.c_int64)),
-                  C.cast(keep[2], C.POINTER(C.c_int32)), B)
-    return desc, dev, keep
+    offs, hw = i64([i * per for i in range(B)]), i32([H, W] * B)
+    desc = Images(C.c_void_p(x.data_ptr()), C.cast(offs, C.POINTER(C.c_int64)), C.cast(hw, C.POINTER(C.c_int32)), B)
+    return desc, dev, [x, offs, hw]
 
 
 def encode(imgs_desc: Images, dev: torch.device, p: FEParams, plan, n_rows: int, seq_len: int,
@@ -549,8 +547,8 @@ def vq_from_indices(cfg: VQCfg, idx: torch.Tensor, project_out: bool) -> torch.T
 class DecodeTable:
     """The host-side image table of one packed batch (the descriptor arguments
     of dctae_decode / dctae_decode_backward / dctae_pixel_loss_forward) and
-    the batch tensors in the layout the library reads.  Building it walks
-    ``ids.cpu()``: the one host synchronisation of a decode."""
+    the batch tensors in the layout the library reads.  Building it from the
+    batch walks ``ids.cpu()``: the one host synchronisation of a decode."""
 
     def __init__(self, p: FEParams, ids, key_pad, positions, channels, patch_sizes, original_sizes):
         self.dev = _check_dev(ids, key_pad, positions, channels)
@@ -561,34 +559,45 @@ class DecodeTable:
         self.ch = channels.long().contiguous()
         # image enumeration: rows in order, ids ascending (FE:619-633); host view
         ids_h = self.ids.cpu()
-        self.lut_w = int(ids_h.max().item()) + 1 if ids_h.numel() else 1
-        lut = [-1] * (self.R * self.lut_w)
-        n_img = 0
-        for r in range(self.R):
-            for im in torch.unique(ids_h[r]).tolist():
-                lut[r * self.lut_w + im] = n_img
-                n_img += 1
-        if n_img > len(patch_sizes) or n_img > len(original_sizes):
+        places = [(r, im) for r in range(self.R) for im in torch.unique(ids_h[r]).tolist()]
+        if len(places) > len(patch_sizes) or len(places) > len(original_sizes):
             raise IndexError("more images in the batch than patch_sizes / original_sizes entries")
-        self.n_img = n_img
+        self._lay_out(p.channels, places, int(ids_h.max().item()) + 1 if ids_h.numel() else 1,
+                      original_sizes, patch_sizes)
+
+    @classmethod
+    def from_layout(cls, p: FEParams, dev, n_rows, seq_len, rows, local_ids, hw, patch_hw) -> "DecodeTable":
+        """the table of a packing layout (image i in row rows[i] under the id
+        local_ids[i], every image hw = (H, W) with the patch grid patch_hw):
+        no device tensor is read, and the batch tensors come with each call"""
+        t = cls.__new__(cls)
+        t.dev, t.R, t.S = dev, n_rows, seq_len
+        places = sorted(zip(rows, local_ids))
+        t._lay_out(p.channels, places, max(local_ids) + 1, [hw] * len(places), [patch_hw] * len(places))
+        return t
+
+    def _lay_out(self, channels, places, lut_w, original_sizes, patch_sizes):
+        """places: (row, id in the row) of image 0, 1, ... in the enumeration order"""
+        self.channels, self.lut_w, self.n_img = channels, lut_w, len(places)
+        lut = [-1] * (self.R * lut_w)
         self.hw, self.phw, self.offs = [], [], []
         total = 0
-        for i in range(n_img):
+        for i, (r, im) in enumerate(places):
+            lut[r * lut_w + im] = i
             h, w = (int(v) for v in original_sizes[i])
             ph, pw = (int(v) for v in patch_sizes[i])
             self.hw += [h, w]
             self.phw += [ph, pw]
             self.offs.append(total)
-            total += p.channels * h * w
+            total += channels * h * w
         self.total = total
-        self.channels = p.channels
-        self.keep = [i32(lut), i32(self.hw), i64(self.offs), i32(self.phw)]
+        self.keep = k = [i32(lut), i32(self.hw), i64(self.offs), i32(self.phw)]
+        self._c = (C.cast(k[0], C.POINTER(C.c_int32)), lut_w, self.n_img, C.cast(k[1], C.POINTER(C.c_int32)),
+                   C.cast(k[2], C.POINTER(C.c_int64)), C.cast(k[3], C.POINTER(C.c_int32)))
 
     def c_args(self):
         """img_lut, lut_w, n_img, out_hw, out_off, patch_hw as the C ABI takes them"""
-        k = self.keep
-        return (C.cast(k[0], C.POINTER(C.c_int32)), self.lut_w, self.n_img, C.cast(k[1], C.POINTER(C.c_int32)),
-                C.cast(k[2], C.POINTER(C.c_int64)), C.cast(k[3], C.POINTER(C.c_int32)))
+        return self._c
 
     def images(self, flat: torch.Tensor) -> List[torch.Tensor]:
         """the (3, H, W) views of a flat buffer in the decode's output layout"""
@@ -598,6 +607,21 @@ class DecodeTable:
 
 def decode_table(p: FEParams, ids, key_pad, positions, channels, patch_sizes, original_sizes) -> DecodeTable:
     return DecodeTable(p, ids, key_pad, positions, channels, patch_sizes, original_sizes)
+
+
+def _decode_call(ctx, cfg: FECfg, table: DecodeTable, ids, key_pad, pos, ch, norm: Optional[Norm],
+                 lfq: Optional[LFQCfg], codes, patches, out, normed: bool):
+    """dctae_decode (from codes, or from patches when codes is None) or, normed,
+    dctae_decode_normed of the packed batch into the flat buffer ``out``; the
+    tensors as the library reads them (int64 / bool / fp32, contiguous)"""
+    batch = (ctx.h, C.byref(cfg), table.R, *table.c_args(), ptr(ids), ptr(key_pad), ptr(pos), ptr(ch))
+    if normed:
+        rc = ctx.lib.dctae_decode_normed(*batch, C.byref(norm), ptr(patches), ptr(out), _lib.stream_ptr(table.dev))
+    else:
+        rc = ctx.lib.dctae_decode(*batch, C.byref(norm) if norm is not None else None,
+                                  C.byref(lfq) if lfq is not None else None, ptr(codes), ptr(patches), ptr(out),
+                                  _lib.stream_ptr(table.dev))
+    ctx.check(rc, "dctae_decode_normed" if normed else "dctae_decode")
 
 
 def pixel_loss_forward(table: DecodeTable, rgb_hat: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
@@ -656,34 +680,16 @@ def decode(p: FEParams, ids: torch.Tensor, key_pad: torch.Tensor, positions: tor
     dev = _check_dev(ids, key_pad, positions, channels, codes, patches)
     if table is None:
         table = decode_table(p, ids, key_pad, positions, channels, patch_sizes, original_sizes)
-    ctx = _lib.context(dev)
-    R, S, ids_c, kp, pos, ch = table.R, table.S, table.ids, table.key_pad, table.pos, table.ch
-    lut_w, n_img, hw, offs, keep = table.lut_w, table.n_img, table.hw, table.offs, table.keep
     out = torch.empty(table.total, dtype=torch.float32, device=dev)
     cc = codes.long().contiguous() if codes is not None else None
     pp = patches.float().contiguous() if patches is not None else None
-    nc = norm.c() if norm is not None else None
+    if normed and (norm is None or codes is not None):
+        raise AssertionError("normed decode needs the PatchNorm state and patches (no codes)")
+    _decode_call(_lib.context(dev), p.c(table.S), table, table.ids, table.key_pad, table.pos, table.ch,
+                 norm.c() if norm is not None else None, lfq, cc, pp, out, normed)
     if normed:
-        if nc is None or codes is not None:
-            raise AssertionError("normed decode needs the PatchNorm state and patches (no codes)")
-        rc = ctx.lib.dctae_decode_normed(ctx.h, C.byref(p.c(S)), R, C.cast(keep[0], C.POINTER(C.c_int32)), lut_w,
-                                         n_img, C.cast(keep[1], C.POINTER(C.c_int32)),
-                                         C.cast(keep[2], C.POINTER(C.c_int64)), C.cast(keep[3], C.POINTER(C.c_int32)),
-                                         ptr(ids_c), ptr(kp), ptr(pos), ptr(ch), C.byref(nc), ptr(pp), ptr(out),
-                                         _lib.stream_ptr(dev))
-        ctx.check(rc, "dctae_decode_normed")
         check_device_errors(dev)
-    else:
-        rc = ctx.lib.dctae_decode(ctx.h, C.byref(p.c(S)), R, C.cast(keep[0], C.POINTER(C.c_int32)), lut_w, n_img,
-                                  C.cast(keep[1], C.POINTER(C.c_int32)), C.cast(keep[2], C.POINTER(C.c_int64)),
-                                  C.cast(keep[3], C.POINTER(C.c_int32)), ptr(ids_c), ptr(kp), ptr(pos), ptr(ch),
-                                  C.byref(nc) if nc is not None else None, C.byref(lfq) if lfq is not None else None,
-                                  ptr(cc), ptr(pp), ptr(out), _lib.stream_ptr(dev))
-        ctx.check(rc, "dctae_decode")
-    imgs = []
-    for i in range(n_img):
-        h, w = hw[2 * i], hw[2 * i + 1]
-        imgs.append(out[offs[i]: offs[i] + p.channels * h * w].view(p.channels, h, w))
+    imgs = table.images(out)
     return (imgs, out) if return_flat else imgs
 
 

@@ -5,7 +5,7 @@
 //   dctae_api.hip      context, options, timing, scratch growth and plan upload
 //   dctae_plan.hip     DCT matrices, GEMM problems and tile lists, FFT / Bluestein plans
 //   dctae_encode.hip   the encode plan and launch sequence
-//   dctae_decode.hip   the decode launch sequences
+//   dctae_decode.hip   the decode family's planner (DecodeBatch, below) and the decode launch sequences
 //   dctae_decode_bwd.hip  the decode's backward and the pixel loss (kernels and launch sequence)
 //   dctae_api_ops.hip  PatchNorm, LFQ, VectorQuantize and transformer entry points
 #pragma once
@@ -244,6 +244,28 @@ int fft_plan_for(dctae_ctx* ctx, int N, int P, FftPlan* out);
 // the Bluestein block lists of a chunk job are kept per FFT length L
 inline int bs_lidx(int L) { return L == 256 ? 0 : L == 512 ? 1 : L == 1024 ? 2 : 3; }
 constexpr int kBsL[4] = {256, 512, 1024, 2048};
+
+// ---- dctae_decode.hip: what dctae_decode, dctae_decode_normed and dctae_decode_backward share ----
+// the packed batch as the three entry points take it (include/dctae.h)
+struct DecodeBatch {
+  const dctae_fe_cfg* cfg;
+  int32_t n_rows;
+  const int32_t* img_lut;
+  int32_t lut_w, n_img;
+  const int32_t* out_hw;
+  const int64_t* out_off;
+  const int32_t* patch_hw;
+  const int64_t* ids;
+  const uint8_t* key_pad;
+  const int64_t *pos, *ch;
+  hipStream_t s;
+};
+int decode_check(dctae_ctx* ctx, const DecodeBatch& B, const char* own, bool img_bufs, bool tok_bufs);
+int decode_geometry(dctae_ctx* ctx, const DecodeBatch& B, std::vector<ImgDesc>& D, int64_t* max_hw);
+int decode_gemm_pair(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImgDesc& d, float* ws, GemmProblem* g1,
+                     GemmProblem* g2, const float** CW, const float** CH);
+DecodeArgs decode_args(const dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* norm, const dctae_lfq* lfq,
+                       const int64_t* codes, const float* patches, const int32_t* lut, bool normed);
 
 // ---- dctae_encode.hip ----
 void drop_encode_plan(dctae_ctx* ctx);   // dctae_ctx_destroy: EncPlan is complete only there

@@ -315,87 +315,62 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
                           const int32_t* patch_hw, const int64_t* ids, const uint8_t* key_pad, const int64_t* pos,
                           const int64_t* ch, const float* patches, const float* grad_rgb, const float* rgb_hat,
                           const float* rgb, const float* g, float* dpatches, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
+  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch, s};
   if (!ctx) return DCTAE_EINVAL;
   hipSetDevice(ctx->device);
-  int rc = check_cfg(ctx, cfg);
+  int rc = decode_check(ctx, B, nullptr, true, patches && dpatches);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int P = cfg->patch_size, PP = P * P, S = cfg->max_seq_len;
-  if (n_rows < 0 || n_img < 0 || lut_w < 1 || !img_lut || (n_img > 0 && (!out_hw || !out_off || !patch_hw)))
-    return fail(ctx, DCTAE_EINVAL, "bad decode descriptor");
-  if (n_rows > 0 && (!ids || !key_pad || !pos || !ch || !patches || !dpatches))
-    return fail(ctx, DCTAE_EINVAL, "NULL batch tensor");
+  const int PP = cfg->patch_size * cfg->patch_size;
   if (n_img > 0 && !grad_rgb && (!rgb_hat || !rgb || !g))
     return fail(ctx, DCTAE_EINVAL, "decode backward needs grad_rgb, or rgb_hat, rgb and the upstream scalar");
   if (n_img > 65535) return fail(ctx, DCTAE_EUNSUP, "decode backward: more than 65535 images in one call");
   if (n_rows == 0) return 0;
-  const int64_t n_tok = (int64_t)n_rows * S;
+  const int64_t n_tok = (int64_t)n_rows * cfg->max_seq_len;
   if (n_tok > ((int64_t)1 << 31) - 1) return fail(ctx, DCTAE_EUNSUP, "decode backward: too many tokens in one call");
-  for (int64_t i = 0; i < (int64_t)n_rows * lut_w; ++i)
-    if (img_lut[i] < -1 || img_lut[i] >= n_img) return fail(ctx, DCTAE_EINVAL, "image LUT entry out of range");
+  std::vector<ImgDesc> D;
+  int64_t wsf = 0, max_hw;
+  if ((rc = decode_geometry(ctx, B, D, &max_hw))) return rc;
   // workspace: every Y first (one memset), then U / T and ipt / g_ipt per image,
   // each on a 64-float boundary; then the slot map
-  std::vector<ImgDesc> D(std::max(n_img, 1));
-  int64_t wsf = 0, max_hw = 1;
-  for (int i = 0; i < n_img; ++i) {
-    ImgDesc& d = D[i];
-    std::memset(&d, 0, sizeof(d));
-    d.plan_w = d.plan_h = -1;
-    d.H = out_hw[2 * i];
-    d.W = out_hw[2 * i + 1];
-    d.ph = patch_hw[2 * i];
-    d.pw = patch_hw[2 * i + 1];
-    if (d.ph < 1 || d.pw < 1 || P * d.ph > d.H || P * d.pw > d.W)
-      return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": patch_sizes do not fit original_sizes (FE:304)");
-    if (out_off[i] < 0) return fail(ctx, DCTAE_EINVAL, "negative image offset");
-    d.qh = std::min(d.ph, cfg->max_patch_h);
-    d.qw = std::min(d.pw, cfg->max_patch_w);
-    d.Kh = P * d.qh;
-    d.Kw = P * d.qw;
-    d.rgb_off = out_off[i];
+  for (ImgDesc& d : D) {
     d.ws_y = wsf;
     wsf += (3ll * d.Kh * d.Kw + 63) & ~63ll;
-    max_hw = std::max<int64_t>(max_hw, (int64_t)d.H * d.W);
   }
   const int64_t y_floats = wsf;
-  for (int i = 0; i < n_img; ++i) {
-    ImgDesc& d = D[i];
+  for (ImgDesc& d : D) {
     d.ws_t = wsf;
     wsf += (3ll * d.H * d.Kw + 63) & ~63ll;
     d.ws_p = wsf;
     wsf += (3ll * d.H * d.W + 63) & ~63ll;
   }
+  D.resize(std::max(n_img, 1));   // the plan holds a descriptor even without images
   const int64_t gmap_off = wsf;
   const int64_t gmap_n = (int64_t)n_img * 3 * cfg->max_patch_h * cfg->max_patch_w;
   const int64_t dc_off = (gmap_off + gmap_n + 63) & ~63ll;   // the images' DC coefficients, 3 floats each
   OrderedCall oc(ctx, s);
   float* ws;
   if ((rc = oc.scratch(kWs, std::max<size_t>((size_t)(dc_off + 3ll * n_img) * 4, 512), &ws))) return rc;
-  const int rows_cap = P * std::max(cfg->max_patch_h, cfg->max_patch_w);
   std::vector<GemmProblem> probs;
   std::vector<TileRef> t1, t2, t3, t4;
   for (int i = 0; i < n_img; ++i) {
     const ImgDesc& d = D[i];
     const float *CW, *CH;
-    if ((rc = dct_matrix(ctx, d.W, std::min(d.W, rows_cap), &CW))) return rc;
-    if ((rc = dct_matrix(ctx, d.H, std::min(d.H, rows_cap), &CH))) return rc;
+    GemmProblem gs[4];
     // the decode's pair: U[c][y][kx] = sum_ky CH[ky][y] Y[c][ky][kx];  ipt[c][y][x] = sum_kx U[c][y][kx] CW[kx][x]
-    GemmProblem g1 = gemm(CH, 0, 1, d.H, ws + d.ws_y, (int64_t)d.Kh * d.Kw, 1, d.Kw, ws + d.ws_t,
-                          (int64_t)d.H * d.Kw, d.Kw, 1, d.H, d.Kw, d.Kh, 3);
-    GemmProblem g2 = gemm(ws + d.ws_t, (int64_t)d.H * d.Kw, d.Kw, 1, CW, 0, 1, d.W, ws + d.ws_p,
-                          (int64_t)d.H * d.W, d.W, 1, d.H, d.W, d.Kw, 3);
+    if ((rc = decode_gemm_pair(ctx, cfg, d, ws, &gs[0], &gs[1], &CW, &CH))) return rc;
     // its adjoint, truncated to the kept corner:
     // T[c][y][kx] = sum_x g_ipt[c][y][x] CW[kx][x];  dY[c][ky][kx] = sum_y CH[ky][y] T[c][y][kx]
-    GemmProblem g3 = gemm(ws + d.ws_p, (int64_t)d.H * d.W, d.W, 1, CW, 0, d.W, 1, ws + d.ws_t,
-                          (int64_t)d.H * d.Kw, d.Kw, 1, d.H, d.Kw, d.W, 3);
-    GemmProblem g4 = gemm(CH, 0, d.H, 1, ws + d.ws_t, (int64_t)d.H * d.Kw, 1, d.Kw, ws + d.ws_y,
-                          (int64_t)d.Kh * d.Kw, d.Kw, 1, d.Kh, d.Kw, d.H, 3);
-    GemmProblem* gs[4] = {&g1, &g2, &g3, &g4};
+    gs[2] = gemm(ws + d.ws_p, (int64_t)d.H * d.W, d.W, 1, CW, 0, d.W, 1, ws + d.ws_t, (int64_t)d.H * d.Kw, d.Kw, 1,
+                 d.H, d.Kw, d.W, 3);
+    gs[3] = gemm(CH, 0, d.H, 1, ws + d.ws_t, (int64_t)d.H * d.Kw, 1, d.Kw, ws + d.ws_y, (int64_t)d.Kh * d.Kw, d.Kw, 1,
+                 d.Kh, d.Kw, d.H, 3);
+    attach_x3(ctx, gs[2]);
+    attach_x3(ctx, gs[3]);
     std::vector<TileRef>* ts[4] = {&t1, &t2, &t3, &t4};
     for (int k = 0; k < 4; ++k) {
-      attach_x3(ctx, *gs[k]);
-      add_tiles(*ts[k], (int)probs.size(), *gs[k]);
-      probs.push_back(*gs[k]);
+      add_tiles(*ts[k], (int)probs.size(), gs[k]);
+      probs.push_back(gs[k]);
     }
   }
   if (ctx->opt.xcd_order) {   // speed only
@@ -416,19 +391,7 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
   if ((rc = oc.upload(pb, &pd))) return rc;
   const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
   const GemmProblem* gp = (const GemmProblem*)(pd + g_off);
-  DecodeArgs a{};
-  a.ids = ids;
-  a.key_pad = key_pad;
-  a.pos = pos;
-  a.ch = ch;
-  a.patches = patches;
-  a.lut = (const int32_t*)(pd + lut_off);
-  a.lut_w = lut_w;
-  a.S = S;
-  a.P = P;
-  a.maxph = cfg->max_patch_h;
-  a.maxpw = cfg->max_patch_w;
-  a.err = ctx->err_dev;
+  const DecodeArgs a = decode_args(ctx, B, nullptr, nullptr, nullptr, patches, (const int32_t*)(pd + lut_off), false);
   int32_t* gmap = (int32_t*)(ws + gmap_off);
   if (n_img > 0) {
     HIPCHK(ctx, hipMemsetAsync(ws, 0, (size_t)y_floats * 4, s));

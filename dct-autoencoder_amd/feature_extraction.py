@@ -620,70 +620,40 @@ class BatchDecoder:
     order, image ids ascending, FE:619-633) into one (B, 3, H, W) tensor."""
 
     def __init__(self, enc: "BatchEncoder", patchnorm, lfq):
-        import ctypes as C
-        from ._lib import i32, i64
         self.enc = enc
-        pl = enc.plan
-        order = sorted(range(enc.B), key=lambda i: (pl.row[i], pl.local_id[i]))
-        self.lut_w = max(pl.local_id) + 1
-        lut = [-1] * (enc.n_rows * self.lut_w)
-        for n, i in enumerate(order):
-            lut[pl.row[i] * self.lut_w + pl.local_id[i]] = n
-        H, W, p = enc.H, enc.W, enc.fe.patch_size
-        per = 3 * H * W
-        self._keep = [i32(lut), i32([H, W] * enc.B), i64([n * per for n in range(enc.B)]),
-                      i32([H // p, W // p] * enc.B)]
-        self._ptr = [C.cast(self._keep[0], C.POINTER(C.c_int32)), C.cast(self._keep[1], C.POINTER(C.c_int32)),
-                     C.cast(self._keep[2], C.POINTER(C.c_int64)), C.cast(self._keep[3], C.POINTER(C.c_int32))]
+        pl, p = enc.plan, enc.fe.patch_size
+        self.table = _ops.DecodeTable.from_layout(enc.p, enc.dev, enc.n_rows, enc.S, pl.row, pl.local_id,
+                                                  (enc.H, enc.W), (enc.H // p, enc.W // p))
         self.norm = patchnorm.state(thresholds=False)
         self._ncfg = self.norm.c()
         self.lcfg = lfq.cfg()
         self.lfq, self.patchnorm = lfq, patchnorm
-        # LFQ with projections (lfq.py:54-62): codes -> project_out (fused MFMA
-        # kernel, dctae_lfq_project_out) -> inverse PatchNorm (dctae_norm_inverse)
-        # -> the fused decode from tokens
         self.proj = lfq.has_projections
-        # projections: project_out alone (dctae_lfq_project_out) and the
-        # inverse PatchNorm inside the decode's column kernel
-        # (dctae_decode_normed: per-block (c, strip) tables instead of a
-        # per-token table gather); False: project_out with the inverse fused
-        # (dctae_lfq_project_out_inverse_norm) then dctae_decode
+        # LFQ with projections (lfq.py:54-62).  True: project_out alone (dctae_lfq_project_out) and the inverse
+        # PatchNorm inside the decode's column kernel (dctae_decode_normed: per-block (c, strip) tables instead
+        # of a per-token table gather); False: project_out with the inverse fused
+        # (dctae_lfq_project_out_inverse_norm), then dctae_decode
         self.normed_decode = True
-        self.out = torch.empty((enc.B, 3, H, W), dtype=torch.float32, device=enc.dev)
+        self.out = torch.empty((enc.B, 3, enc.H, enc.W), dtype=torch.float32, device=enc.dev)
+
+    def _decode(self, packed, norm, lcfg, codes, patches, normed=False) -> torch.Tensor:
+        e = self.enc
+        _ops._decode_call(e.ctx, e._cfg, self.table, packed["image_ids"], packed["key_pad_mask"],
+                          packed["positions"], packed["channels"], norm, lcfg, codes, patches, self.out, normed)
+        return self.out
 
     def __call__(self, packed) -> torch.Tensor:
-        from ._lib import ptr, stream_ptr
-        import ctypes as C
         e = self.enc
-        lut, hw, offs, phw = self._ptr
-        if self.proj:
-            from . import _ops
-            if self.lfq._fused_proj() and self.normed_decode:
-                w, b = self.lfq._proj_w(self.lfq.project_out, e.dev)
-                x = _ops.lfq_project_out(packed["codes"], w, b, self.lcfg)
-                rc = e.ctx.lib.dctae_decode_normed(e.ctx.h, C.byref(e._cfg), e.n_rows, lut, self.lut_w, e.B, hw, offs,
-                                                   phw, ptr(packed["image_ids"]), ptr(packed["key_pad_mask"]),
-                                                   ptr(packed["positions"]), ptr(packed["channels"]),
-                                                   C.byref(self._ncfg), ptr(x), ptr(self.out), stream_ptr(e.dev))
-                e.ctx.check(rc, "dctae_decode_normed")
-                return self.out
-            if self.lfq._fused_proj():
-                w, b = self.lfq._proj_w(self.lfq.project_out, e.dev)
-                x = _ops.lfq_project_out_inverse_norm(packed["codes"], w, b, self.lcfg, self.norm, e.fe.params(),
-                                                      packed["channels"], packed["positions"])
-            else:
-                x = self.lfq.indices_to_codes(packed["codes"]).float()
-                x = _ops.norm_apply(x, packed["channels"], packed["positions"], self.norm, e.fe.params(),
-                                    inverse=True)
-            rc = e.ctx.lib.dctae_decode(e.ctx.h, C.byref(e._cfg), e.n_rows, lut, self.lut_w, e.B, hw, offs, phw,
-                                        ptr(packed["image_ids"]), ptr(packed["key_pad_mask"]),
-                                        ptr(packed["positions"]), ptr(packed["channels"]), None, None, None, ptr(x),
-                                        ptr(self.out), stream_ptr(e.dev))
-            e.ctx.check(rc, "dctae_decode")
-            return self.out
-        rc = e.ctx.lib.dctae_decode(e.ctx.h, C.byref(e._cfg), e.n_rows, lut, self.lut_w, e.B, hw, offs, phw,
-                                    ptr(packed["image_ids"]), ptr(packed["key_pad_mask"]), ptr(packed["positions"]),
-                                    ptr(packed["channels"]), C.byref(self._ncfg), C.byref(self.lcfg),
-                                    ptr(packed["codes"]), None, ptr(self.out), stream_ptr(e.dev))
-        e.ctx.check(rc, "dctae_decode")
-        return self.out
+        if not self.proj:
+            return self._decode(packed, self._ncfg, self.lcfg, packed["codes"], None)
+        if not self.lfq._fused_proj():
+            x = self.lfq.indices_to_codes(packed["codes"]).float()
+            x = _ops.norm_apply(x, packed["channels"], packed["positions"], self.norm, e.fe.params(), inverse=True)
+            return self._decode(packed, None, None, None, x)
+        w, b = self.lfq._proj_w(self.lfq.project_out, e.dev)
+        if self.normed_decode:
+            x = _ops.lfq_project_out(packed["codes"], w, b, self.lcfg)
+            return self._decode(packed, self._ncfg, None, None, x, normed=True)
+        x = _ops.lfq_project_out_inverse_norm(packed["codes"], w, b, self.lcfg, self.norm, e.fe.params(),
+                                              packed["channels"], packed["positions"])
+        return self._decode(packed, None, None, None, x)

@@ -404,7 +404,8 @@ int dctae_vq_output_from_indices(dctae_ctx* ctx, const dctae_vq* vq, const int64
  * (FE:628 image_ids.unique()).  img_lut (host, n_rows x lut_w) maps
  * (row, image id) -> image index (or -1); out_hw / out_off / patch_hw (host,
  * per image) give the original size, the output element offset in rgb_dev
- * and the (uncapped) patch_sizes. */
+ * and the (uncapped) patch_sizes.  A negative out_off entry is refused
+ * (DCTAE_EINVAL, "negative image offset") before anything is launched. */
 int dctae_decode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut,
                  int32_t lut_w, int32_t n_img, const int32_t* out_hw, const int64_t* out_off,
                  const int32_t* patch_hw, const int64_t* image_ids_dev, const uint8_t* key_pad_dev,
@@ -421,7 +422,8 @@ int dctae_decode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const 
  * geometries as dctae_norm_inverse into the context's staging buffer first.
  * Replaces inv_normalize_ (modeling_dct_autoencoder.py:122-127) + the
  * processor's postprocess (FE:289-310) after LFQ.indices_to_codes with
- * projections (the codes path: dctae_decode with codes_dev). */
+ * projections (the codes path: dctae_decode with codes_dev).  A negative
+ * out_off entry is refused as dctae_decode refuses it. */
 int dctae_decode_normed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut,
                         int32_t lut_w, int32_t n_img, const int32_t* out_hw, const int64_t* out_off,
                         const int32_t* patch_hw, const int64_t* image_ids_dev, const uint8_t* key_pad_dev,

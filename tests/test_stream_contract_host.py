@@ -149,10 +149,11 @@ def _sources(suffixes):
 
 
 def _bodies():
-    """name -> body text of every extern "C" function, helpers they call by name included once"""
+    """name -> body text of every extern "C" function, helpers they call by name included once
+    (host functions of any plain return type: ``int``, ``void``, a struct by value)"""
     text = "\n".join(_sources(".hip").values())
     funcs = {}
-    for m in re.finditer(r"^(?:static\s+)?(?:int|void)\s+(?:dctae::)?(\w+)\s*\([^;{]*?\)\s*(?:const\s*)?\{", text,
+    for m in re.finditer(r"^(?:static\s+)?[\w:]+\s+(?:dctae::)?(\w+)\s*\([^;{]*?\)\s*(?:const\s*)?\{", text,
                          flags=re.M | re.S):
         i, depth = m.end(), 1
         while depth and i < len(text):
