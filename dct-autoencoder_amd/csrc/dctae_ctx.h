@@ -5,6 +5,7 @@
 //   dctae_api.hip      context, options, timing, scratch growth and plan upload
 //   dctae_plan.hip     DCT matrices, GEMM problems and tile lists, FFT / Bluestein plans
 //   dctae_encode.hip   the encode plan and launch sequence
+//   dctae_enc_layout.h the encode plan's routes, workspace regions, chunk cut and staging carve (no HIP calls)
 //   dctae_decode.hip   the decode family's planner (DecodeBatch, below) and the decode launch sequences
 //   dctae_decode_bwd.hip  the decode's backward and the pixel loss (kernels and launch sequence)
 //   dctae_api_ops.hip  PatchNorm, LFQ, VectorQuantize and transformer entry points
@@ -160,6 +161,14 @@ struct Timer {
 };
 
 // ---- plan serialisation ----------------------------------------------------
+// a list of the plan: where it starts in the buffer, how many T it holds
+template <class T>
+struct PlanList {
+  size_t off = 0;
+  int n = 0;
+  const T* at(const uint8_t* pd) const { return reinterpret_cast<const T*>(pd + off); }
+};
+
 struct PlanBuf {
   std::vector<uint8_t> bytes;
   template <class T>
@@ -168,6 +177,11 @@ struct PlanBuf {
     bytes.resize(off + n * sizeof(T));
     if (n) std::memcpy(bytes.data() + off, p, n * sizeof(T));
     return off;
+  }
+  // an empty list is added too: it pads the buffer to the next 256 bytes
+  template <class T>
+  PlanList<T> add(const std::vector<T>& v) {
+    return {add(v.data(), v.size()), (int)v.size()};
   }
 };
 
@@ -236,6 +250,7 @@ int describe(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int H, int W, ImgDesc& d);
 GemmProblem gemm(const float* A, int64_t sAc, int64_t sAm, int64_t sAk, const float* B, int64_t sBc, int64_t sBn,
                  int64_t sBk, float* O, int64_t sOc, int64_t sOm, int64_t sOn, int M, int N, int K, int C);
 void xcd_deal_tiles(std::vector<TileRef>& t, const GemmProblem* probs, int share);
+void xcd_deal_col_blocks(std::vector<int4>& L);
 void add_tiles(std::vector<TileRef>& t, int prob, const GemmProblem& g);
 EncParams enc_params(const dctae_fe_cfg* cfg, const dctae_norm* norm, const dctae_lfq* lfq);
 int next_pow2(int x);

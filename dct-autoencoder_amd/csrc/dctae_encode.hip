@@ -1,399 +1,56 @@
 // The encode engine: plan, plan cache and launch sequence of dctae_encode,
 // dctae_spectrum_tokens, dctae_dct2 and dctae_patch_spectrum.
 #include "dctae_ctx.h"
+#include "dctae_enc_layout.h"
 
 using namespace dctae;
 
 // Encode plan: everything the launch sequence needs, cached on the inputs.
 constexpr int kVariants = 3;  // 0 = generic FFT kernels, 1.. = dctae_fft2.hip specialisations
 
+struct FftTables {
+  int64_t tw_off, post_off;   // a compile-time plan kernel's tables in the context's FFT table buffer (FftPlan)
+};
+
 struct ChunkJob {
   int i0, i1;
-  size_t desc_off, gp_off, rows_t_off, cols_t_off;
-  size_t fr_off[kVariants], fc_off[kVariants];
-  int n_fr[kVariants], n_fc[kVariants];
-  int64_t tw_off[kVariants], post_off_r[kVariants], tw_off_c[kVariants], post_off_c[kVariants];
-  int n_rows_tiles, n_cols_tiles;
-  size_t pc_off;      // k_fft_cols7 list: the spec-1 images of the job (one tile-column count qw)
-  int n_pc, pc_qw;
-  size_t pb_off;      // k_cols512b list: the band-layout images of the job
-  int n_pb;
-  int max_T, any_gemm_rows, any_gemm_cols, fold_t, any_bs_cols;
-  size_t ipt_off;            // k_rgb_to_ipt blocks (local image, first group)
-  int n_ipt;
-  size_t fold_off;           // local indices of the images whose T k_fold_t folds
-  int n_fold;
+  PlanList<ImgDesc> desc;
+  PlanList<GemmProblem> gp;
+  PlanList<TileRef> rows_t, cols_t;   // the GEMMs' tiles
+  PlanList<TileRef> fused_t;          // k_rows_fused tiles (row problem, row-pair block)
+  PlanList<int2> fr[kVariants];       // FFT row blocks (local image, first row) per kernel variant
+  PlanList<int4> fc[kVariants];       // FFT column blocks (local image, channel, tile column, count)
+  FftTables row_tab[kVariants], col_tab[kVariants];
+  PlanList<int32_t> pc;   // k_fft_cols7 list: the spec-1 images of the job (one tile-column count qw)
+  int n_pc, pc_qw;        // n_pc = pc.n when one persistent launch serves all of them, else 0
+  PlanList<int32_t> pb;   // k_cols512b list: the band-layout images of the job
+  int max_T;
+  PlanList<int2> ipt;       // k_rgb_to_ipt blocks (local image, first group)
+  PlanList<int32_t> fold;   // local indices of the images whose T k_fold_t folds
   int64_t fold_max_hw;
-  size_t br_off[4], bc_off[4];   // Bluestein row / column blocks per L = 256 .. 2048
-  int n_br[4], n_bc[4];
-  int64_t max_hw;
+  PlanList<int2> br[4];   // Bluestein row / column blocks per L = 256 .. 2048
+  PlanList<int4> bc[4];
   size_t lds_rows, lds_cols;
-  int64_t amax_off;   // k_gemm_h2: |max| bits per image (IPT, T) in the workspace, floats
-  int h2;             // the job's GEMMs on k_gemm_h2
-  size_t epi_off;     // k_tile_epilogue_p blocks (local image, 3 h + c) of the images with Y in the workspace
-  int n_epi;
-  size_t fused_t_off;  // k_rows_fused tiles (row problem, row-pair block)
-  int n_fused_tiles, any_fused;
+  int64_t amax_off;     // k_gemm_h2: |max| bits per image (IPT, T) in the workspace, floats
+  int h2;               // the job's GEMMs on k_gemm_h2
+  PlanList<int2> epi;   // k_tile_epilogue_p blocks (local image, 3 h + c) of the images with Y in the workspace
 };
 
 struct EncPlan {
   uint64_t id = 0;
   PlanBuf pb;
   std::vector<ChunkJob> jobs;
-  size_t all_desc_off = 0;   // every image, global token offsets (sort_pack)
+  PlanList<ImgDesc> all_desc;   // every image, global token offsets (sort_pack)
+  PlanList<int32_t> rowlen;
+  PlanList<FftPlan> plans;
   int n_img = 0, max_T = 1;
   int64_t n_tok = 0;
-  size_t rowlen_off = 0, plans_off = 0;
-  size_t ws_need = 0, st_need = 0;
+  size_t ws_need = 0;
+  StageLayout stage;     // the token staging: its scratch request and token_sinks' carve
   float* ws = nullptr;   // the workspace its GEMM problems point into: the plan drops when the workspace moves
-  int ncb = 0;
   bool any_pad = true;   // some packed row shorter than max_seq_len
   bool uniform = false;  // every image of the call has the same (H, W)
 };
-
-// The encode engine.  Full mode (pack != NULL): packed DCTPatches outputs.
-// Token mode (pack == NULL): spectrum tokens in flat order (tokens_dev /
-// scores_dev at tok_off).  Per image the row DCT (length W) and the column
-// DCT (length H) each run on the FFT kernels when the length has a plan, else
-// on the MFMA GEMM; the intermediate T[c][y][kx] (3, H, Kw) is shared.
-static int build_encode_plan(OrderedCall& oc, const dctae_fe_cfg* cfg, const dctae_images* imgs,
-                             const dctae_packing* pack, bool full, int ncb, bool want_raw, bool want_norm,
-                             const int64_t* tok_off_user, EncPlan& E) {
-  dctae_ctx* ctx = oc.ctx;
-  const int n = imgs->n_img;
-  const int P = cfg->patch_size, PP = P * P, S = cfg->max_seq_len;
-  int rc;
-  std::vector<ImgDesc> D(n);
-  std::vector<FftPlan> plans;
-  std::map<int, int> plan_idx;
-  auto plan_of = [&](int N) -> int {
-    auto it = plan_idx.find(N);
-    if (it != plan_idx.end()) return it->second;
-    FftPlan p;
-    int idx = -1;
-    if (fft_plan_for(ctx, N, P, &p) == 0 || bs_plan_for(ctx, N, &p) == 0) {
-      idx = (int)plans.size();
-      plans.push_back(p);
-    }
-    plan_idx[N] = idx;
-    return idx;
-  };
-  for (int i = 0; i < n; ++i) {
-    if ((rc = describe(ctx, cfg, imgs->hw[2 * i], imgs->hw[2 * i + 1], D[i]))) return rc;
-    D[i].rgb_off = imgs->img_off[i];
-    if (full) {
-      D[i].row = pack->row[i];
-      D[i].col = pack->col[i];
-      D[i].k = pack->k[i];
-      D[i].local_id = pack->local_id[i];
-      if (D[i].k < 1 || D[i].k > D[i].T || D[i].k > S)
-        return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": k out of range (FE:429-435)");
-      if (D[i].row < 0 || D[i].row >= pack->n_rows || D[i].col < 0 || D[i].col + D[i].k > S)
-        return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": packed span outside (rows, S)");
-    }
-    D[i].plan_w = plan_of(D[i].W);
-    D[i].plan_h = plan_of(D[i].H);
-    D[i].bs = (D[i].plan_w >= 0 && plans[D[i].plan_w].kind == 1 ? 1 : 0) |
-              (D[i].plan_h >= 0 && plans[D[i].plan_h].kind == 1 ? 2 : 0);
-    D[i].tperm = ctx->opt.tperm && D[i].plan_w < 0 && D[i].plan_h < 0;
-    // band layout: rows on k_rows512pk (Kw = 448) and columns on k_cols512b (Kh = 448)
-    D[i].tband = ctx->opt.cols512b && ctx->opt.rows_kernel == 4 && cfg->max_patch_w == 32 && cfg->max_patch_h == 32 &&
-                 D[i].H == 512 && D[i].W == 512 && D[i].Kh == 448 && D[i].Kw == 448 && D[i].bs == 0 && D[i].plan_w >= 0 &&
-                 plans[D[i].plan_w].spec == 1 && D[i].plan_h >= 0 && plans[D[i].plan_h].spec == 1;
-    // packed encodes of band images: item-major token staging (stage_pos; the
-    // staging is internal there, while dctae_spectrum_tokens hands it out in flat order)
-    if (full && D[i].tband) D[i].tband |= 2;
-  }
-  if (full)
-    for (int r = 0; r < pack->n_rows; ++r)
-      if (pack->row_len[r] < 0 || pack->row_len[r] > S) return fail(ctx, DCTAE_EINVAL, "row_len out of range");
-  // chunks: FFT images are grouped so the intermediate T of a chunk stays in
-  // the 256 MiB Infinity Cache between the row and column kernels
-  auto ws_of = [&](const ImgDesc& d) {
-    int64_t w = 3ll * d.Kw * d.H + 64;
-    if (d.plan_w < 0) w += 3ll * d.H * d.W + 64;
-    if (d.plan_h < 0 || (d.bs & 2)) w += 3ll * d.Kh * d.Kw + 64;
-    return w * 4;
-  };
-  auto st_of = [&](const ImgDesc& d) {
-    return (int64_t)d.T * (4 + 2 * ncb + (want_raw && full ? 4 * PP : 0) + (want_norm ? 4 * PP : 0));
-  };
-  for (int i = 0; i < n;) {
-    ChunkJob j{};
-    j.i0 = i;
-    int64_t wsb = 0;
-    while (i < n) {
-      const int64_t w = ws_of(D[i]);
-      const bool fft = D[i].plan_w >= 0 && D[i].plan_h >= 0;
-      const int64_t cap = fft ? std::min<int64_t>(ctx->opt.chunk_bytes, ctx->opt.ws_limit) : ctx->opt.ws_limit;
-      if (i > j.i0 && wsb + w > cap) break;
-      wsb += w;
-      ++i;
-    }
-    j.i1 = i;
-    E.jobs.push_back(j);
-  }
-  const int rows_cap = P * std::max(cfg->max_patch_h, cfg->max_patch_w);
-  std::vector<GemmProblem> probs;
-  int64_t tok = 0;
-  for (auto& j : E.jobs) {
-    int64_t wsf = 0;
-    j.max_T = 1;
-    j.max_hw = 1;
-    auto up = [](int64_t v) { return (v + 63) & ~63ll; };  // 256-byte aligned regions (float4 strip loads)
-    for (int i = j.i0; i < j.i1; ++i) {
-      ImgDesc& d = D[i];
-      if (ctx->opt.t_alias > 0 && i - j.i0 >= ctx->opt.t_alias) {   // profiling: T slots shared (wrong output)
-        d.ws_t = D[j.i0 + (i - j.i0) % ctx->opt.t_alias].ws_t;
-        d.ws_p = d.ws_y = wsf;
-        d.tok_off = full ? tok : tok_off_user[i];
-        tok += d.T;
-        j.max_T = std::max(j.max_T, d.T);
-        j.max_hw = std::max<int64_t>(j.max_hw, (int64_t)d.H * d.W);
-        continue;
-      }
-      d.ws_t = wsf;
-      wsf += up(3ll * d.Kw * d.H);
-      d.ws_p = wsf;
-      if (d.plan_w < 0) wsf += up(3ll * d.H * d.W);
-      d.ws_y = wsf;
-      if (d.plan_h < 0 || (d.bs & 2)) wsf += up(3ll * d.Kh * d.Kw);
-      d.tok_off = full ? tok : tok_off_user[i];
-      tok += d.T;
-      j.max_T = std::max(j.max_T, d.T);
-      j.max_hw = std::max<int64_t>(j.max_hw, (int64_t)d.H * d.W);
-    }
-    j.amax_off = wsf;
-    wsf += up(3ll * (j.i1 - j.i0) + 9);   // |max| pairs, then k_rows_fused's per-image flags, "any" word, 8 tile counters
-    E.ws_need = std::max<size_t>(E.ws_need, (size_t)wsf * 4);
-    E.max_T = std::max(E.max_T, j.max_T);
-  }
-  E.n_tok = tok;
-  E.n_img = n;
-  E.uniform = true;
-  for (int i = 1; i < n; ++i) E.uniform = E.uniform && D[i].H == D[0].H && D[i].W == D[0].W;
-  {
-    int64_t st = 0;
-    for (int i = 0; i < n; ++i) st += st_of(D[i]);
-    E.st_need = (size_t)st + 4096;
-  }
-  // both buffers are sized where the plan is built (token_sinks carves the staging)
-  uint8_t* st;
-  if ((rc = oc.scratch(kWs, std::max<size_t>(E.ws_need, 256), &E.ws)) ||
-      (rc = oc.scratch(kStage, std::max<size_t>(E.st_need, 256), &st)))
-    return rc;
-  float* ws = E.ws;
-  for (auto& j : E.jobs) {
-    j.desc_off = E.pb.add(D.data() + j.i0, j.i1 - j.i0);
-    const size_t p0 = probs.size();
-    std::vector<TileRef> rt, ct, ft;
-    std::vector<int2> fr[kVariants];
-    std::vector<int4> fc[kVariants];
-    std::vector<int2> br[4];
-    std::vector<int4> bc[4];
-    std::vector<int32_t> fold;
-    std::vector<int2> ipt;
-    std::vector<int32_t> pc, pb;
-    std::vector<int2> epi;
-    int pc_qw = 0;
-    bool pc_ok = cfg->max_patch_h <= 32;   // k_fft_cols7 keeps Kh <= 448 rows
-    j.lds_rows = j.lds_cols = 0;
-    for (int i = j.i0; i < j.i1; ++i) {
-      const ImgDesc& d = D[i];
-      const int li = i - j.i0;
-      if (d.plan_w < 0) {
-        // T[c][y][kx] = sum_x CW[kx][x] * IPT[c][y][x], folded: even kx over
-        // IPT[x] + IPT[W-1-x], odd kx over IPT[x] - IPT[W-1-x] (half the flops)
-        const size_t q0 = probs.size();
-        for (int par = 0; par < 2; ++par) {
-          const int M = par ? d.Kw / 2 : (d.Kw + 1) / 2, K = par ? d.W / 2 : (d.W + 1) / 2;
-          if (M == 0) continue;
-          const float* CW;
-          if ((rc = dct_matrix(ctx, d.W, std::min(d.W, rows_cap), &CW, par))) return rc;
-          // A: the folded IPT (k_rgb_to_ipt), u at x < ceil(W/2), v after it; B:
-          // the half DCT matrix (shared by the channels).  T rows y are the GEMM
-          // rows, so a wave's stores run along kx (the accumulator's lane-fast
-          // dimension; with the roles swapped they strided by Kw floats)
-          // parity-planar T (tperm: the columns are GEMMs too): each parity's
-          // outputs are contiguous runs (interleaved stores made every line
-          // twice-written: 4.4 GB of writes for 2.7 GB of T on config 4)
-          GemmProblem g = d.tperm ? gemm(ws + d.ws_p + (par ? (d.W + 1) / 2 : 0), (int64_t)d.H * d.W, d.W, 1, CW, 0,
-                                         K, 1, ws + d.ws_t + (par ? (d.Kw + 1) / 2 : 0), (int64_t)d.Kw * d.H, d.Kw,
-                                         1, d.H, M, K, 3)
-                                  : gemm(ws + d.ws_p + (par ? (d.W + 1) / 2 : 0), (int64_t)d.H * d.W, d.W, 1, CW, 0,
-                                         K, 1, ws + d.ws_t + par, (int64_t)d.Kw * d.H, d.Kw, 2, d.H, M, K, 3);
-          attach_x3(ctx, g);
-          uint32_t* am = reinterpret_cast<uint32_t*>(ws + j.amax_off) + 2 * li;
-          g.amax = am;                               // k_rgb_to_ipt's |max| of the folded IPT
-          g.omax = d.plan_h < 0 ? am + 1 : nullptr;  // T's |max| for the column GEMM
-          g.pad2 = li;                               // k_rows_fused: the image and the parity
-          g.pad3 = par;
-          probs.push_back(g);
-        }
-        // k_rows_fused (colour transform + folds + row GEMM in one pass) for the
-        // tperm images whose parity matrices are cached pre-split (both forms:
-        // the fix-up runs the bf16 one) and fit its 256 output columns
-        bool fz = ctx->opt.rows_fused && d.tperm && probs.size() == q0 + 2;   // both parities, consecutive
-        for (size_t q = q0; q < probs.size(); ++q) fz = fz && probs[q].Xh && probs[q].N <= fused_max_n();
-        if (fz)
-          for (int rb = 0; rb * fused_pairs_per_block() < (d.H + 1) / 2; ++rb) ft.push_back(TileRef{(int)(q0 - p0), rb});
-        else
-          for (size_t q = q0; q < probs.size(); ++q) add_tiles(rt, (int)(q - p0), probs[q]);
-        if (fz) {
-          j.any_fused = 1;
-        } else {
-          j.any_gemm_rows = 1;
-          // k_rgb_to_ipt's (x, y)-mirrored pixel groups of this image
-          const int64_t ng = (int64_t)(d.plan_h < 0 ? (d.H + 1) / 2 : d.H) * ((d.W + 1) / 2);
-          for (int64_t g0 = 0; g0 < ng; g0 += rgb_to_ipt_groups_per_block()) ipt.push_back(make_int2(li, (int)g0));
-        }
-      } else if (d.bs & 1) {
-        const int L = plans[d.plan_w].bs_L, rpb = bs_rows_per_block(L);
-        for (int y0 = 0; y0 < d.H; y0 += rpb) br[bs_lidx(L)].push_back(make_int2(li, y0));
-      } else {
-        const FftPlan& p = plans[d.plan_w];
-        for (int y0 = 0; y0 < d.H; y0 += p.rows_per_block) fr[p.spec].push_back(make_int2(li, y0));
-        if (p.spec) {
-          j.tw_off[p.spec] = p.tw_off;
-          j.post_off_r[p.spec] = p.post_off;
-        } else {
-          j.lds_rows = std::max<size_t>(j.lds_rows, (size_t)2 * p.rows_per_block * 3 * (2 * p.M + 1) * 4);
-        }
-      }
-      if (d.plan_h < 0 || (d.bs & 2))   // Y in the workspace: the tile epilogue's (tile row, channel) blocks
-        for (int h = 0; h < d.qh; ++h)
-          for (int c = 0; c < 3; ++c) epi.push_back(make_int2(li, 3 * h + c));
-      if (d.plan_h < 0) {
-        // Y[c][ky][kx] = sum_y CH[ky][y] * T[c][y][kx], folded along y as the rows
-        for (int par = 0; par < 2; ++par) {
-          const int M = par ? d.Kh / 2 : (d.Kh + 1) / 2, K = par ? d.H / 2 : (d.H + 1) / 2;
-          if (M == 0) continue;
-          const float* CH;
-          if ((rc = dct_matrix(ctx, d.H, std::min(d.H, rows_cap), &CH, par))) return rc;
-          // B: T folded along y (by the row GEMM of the y-folded IPT, or in place by
-          // k_fold_t after FFT rows): u in rows m < ceil(H/2), v[m] in row H-1-m
-          GemmProblem g = gemm(CH, 0, K, 1, ws + d.ws_t + (par ? (int64_t)(d.H - 1) * d.Kw : 0),
-                               (int64_t)d.Kw * d.H, 1, par ? -(int64_t)d.Kw : d.Kw,
-                               ws + d.ws_y + (int64_t)par * d.Kw, (int64_t)d.Kh * d.Kw, 2 * (int64_t)d.Kw, 1, M,
-                               d.Kw, K, 3);
-          attach_x3(ctx, g);
-          g.amax = reinterpret_cast<uint32_t*>(ws + j.amax_off) + 2 * li + 1;   // T's |max| (row GEMM / k_fold_t)
-          add_tiles(ct, (int)(probs.size() - p0), g);
-          probs.push_back(g);
-        }
-        j.any_gemm_cols = 1;
-        if (d.plan_w >= 0) {
-          j.fold_t = 1;
-          fold.push_back(li);
-          j.fold_max_hw = std::max<int64_t>(j.fold_max_hw, (int64_t)d.H * d.W);
-        }
-      } else if (d.bs & 2) {
-        const int L = plans[d.plan_h].bs_L, cpb = bs_cols_per_block(L);
-        for (int c = 0; c < 3; ++c)
-          for (int kx0 = 0; kx0 < d.Kw; kx0 += cpb) bc[bs_lidx(L)].push_back(make_int4(li, c, kx0, 0));
-        j.any_bs_cols = 1;
-      } else if (d.tband) {
-        pb.push_back(li);
-        j.tw_off_c[1] = plans[d.plan_h].tw_off;
-        j.post_off_c[1] = plans[d.plan_h].post_off;
-      } else {
-        const FftPlan& p = plans[d.plan_h];
-        // generic kernel: one tile column per block; specialised: groups of
-        // up to 16 adjacent tile columns walked by one block
-        const int G = 1;
-        for (int c = 0; c < 3; ++c)
-          for (int w = 0; w < d.qw; w += G) fc[p.spec].push_back(make_int4(li, c, w, std::min(G, d.qw - w)));
-        if (p.spec == 1) {
-          pc_ok = pc_ok && (pc.empty() || d.qw == pc_qw);
-          pc_qw = d.qw;
-          pc.push_back(li);
-        }
-        if (p.spec) {
-          j.tw_off_c[p.spec] = p.tw_off;
-          j.post_off_c[p.spec] = p.post_off;
-        } else {
-          j.lds_cols = std::max<size_t>(j.lds_cols, (size_t)2 * 2 * p.M * P * 4);
-        }
-      }
-    }
-    // k_gemm_h2 when every GEMM of the job has its shared matrix pre-split
-    j.h2 = ctx->opt.gemm_x3 && ctx->opt.gemm_h2 && probs.size() > p0;
-    for (size_t q = p0; q < probs.size(); ++q) j.h2 = j.h2 && probs[q].Xh != nullptr;
-    j.gp_off = E.pb.add(probs.data() + p0, probs.size() - p0);
-    if (ctx->opt.xcd_order) {
-      xcd_deal_tiles(rt, probs.data() + p0, 1);
-      xcd_deal_tiles(ct, probs.data() + p0, 2);
-      xcd_deal_tiles(ft, probs.data() + p0, 1);   // an image's blocks on one XCD: its two matrices in one L2
-    }
-    j.rows_t_off = E.pb.add(rt.data(), rt.size());
-    j.fused_t_off = E.pb.add(ft.data(), ft.size());
-    j.n_fused_tiles = (int)ft.size();
-    j.cols_t_off = E.pb.add(ct.data(), ct.size());
-    // XCD-aware order of the column blocks (speed only; any order is correct):
-    // blocks b and b+8 are dealt to the same XCD, so give all the blocks of
-    // one (image, channel) the same b % 8 and consecutive b / 8 — the 56-byte
-    // row slices of neighbouring tile columns then share that XCD's L2 lines.
-    if (ctx->opt.xcd_order) {
-      for (int v = 1; v < kVariants; ++v) {
-        std::vector<int4>& L = fc[v];
-        if (L.size() < 16) continue;
-        // units = runs of blocks with the same (image, channel), in list order
-        std::vector<std::pair<size_t, size_t>> units;
-        for (size_t a0 = 0; a0 < L.size();) {
-          size_t a1 = a0 + 1;
-          while (a1 < L.size() && L[a1].x == L[a0].x && L[a1].y == L[a0].y) ++a1;
-          units.push_back({a0, a1});
-          a0 = a1;
-        }
-        std::vector<std::vector<int4>> lanes(8);
-        for (size_t u = 0; u < units.size(); ++u)
-          for (size_t a = units[u].first; a < units[u].second; ++a) lanes[u % 8].push_back(L[a]);
-        std::vector<int4> out;
-        out.reserve(L.size());
-        size_t maxlen = 0;
-        for (auto& l : lanes) maxlen = std::max(maxlen, l.size());
-        for (size_t q = 0; q < maxlen; ++q)
-          for (int x = 0; x < 8; ++x)
-            if (q < lanes[x].size()) out.push_back(lanes[x][q]);
-        L.swap(out);
-      }
-    }
-    for (int v = 0; v < kVariants; ++v) {
-      j.fr_off[v] = E.pb.add(fr[v].data(), fr[v].size());
-      j.fc_off[v] = E.pb.add(fc[v].data(), fc[v].size());
-      j.n_fr[v] = (int)fr[v].size();
-      j.n_fc[v] = (int)fc[v].size();
-    }
-    j.ipt_off = E.pb.add(ipt.data(), ipt.size());
-    j.n_ipt = (int)ipt.size();
-    j.fold_off = E.pb.add(fold.data(), fold.size());
-    j.n_fold = (int)fold.size();
-    for (int l = 0; l < 4; ++l) {
-      j.br_off[l] = E.pb.add(br[l].data(), br[l].size());
-      j.bc_off[l] = E.pb.add(bc[l].data(), bc[l].size());
-      j.n_br[l] = (int)br[l].size();
-      j.n_bc[l] = (int)bc[l].size();
-    }
-    j.n_rows_tiles = (int)rt.size();
-    j.n_cols_tiles = (int)ct.size();
-    // all spec-1 column items of the job in one persistent launch, when their qw agree
-    j.n_pc = (pc_ok && (int)pc.size() * 3 * pc_qw == (int)fc[1].size()) ? (int)pc.size() : 0;
-    j.pc_qw = pc_qw;
-    j.pc_off = E.pb.add(pc.data(), pc.size());
-    j.n_pb = (int)pb.size();
-    j.pb_off = E.pb.add(pb.data(), pb.size());
-    j.n_epi = (int)epi.size();
-    j.epi_off = E.pb.add(epi.data(), epi.size());
-  }
-  E.plans_off = E.pb.add(plans.data(), plans.size());
-  E.all_desc_off = E.pb.add(D.data(), D.size());
-  if (full && pack->n_rows > 0) E.rowlen_off = E.pb.add(pack->row_len, pack->n_rows);
-  E.any_pad = false;
-  if (full)
-    for (int r = 0; r < pack->n_rows; ++r) E.any_pad = E.any_pad || pack->row_len[r] < S;
-  E.ncb = ncb;
-  return 0;
-}
 
 // One encode call: its arguments and what they ask for.
 struct EncCall {
@@ -472,6 +129,294 @@ std::vector<int64_t> EncCall::plan_key(const Options& opt) const {
   return key;
 }
 
+// the images of a call with their routes, and the FFT plans plan_w / plan_h index
+struct EncImages {
+  std::vector<ImgDesc> D;
+  std::vector<FftPlan> plans;
+};
+
+// planner stage 1: describe and validate the images (geometry, packing, routes, tperm, tband)
+static int describe_images(dctae_ctx* ctx, const EncCall& c, EncImages& im) {
+  const dctae_fe_cfg* cfg = c.cfg;
+  const dctae_packing* pack = c.pack;
+  const int n = c.imgs->n_img, P = cfg->patch_size, S = cfg->max_seq_len;
+  int rc;
+  std::vector<ImgDesc>& D = im.D;
+  std::vector<FftPlan>& plans = im.plans;
+  D.resize(n);
+  std::map<int, int> plan_idx;
+  auto plan_of = [&](int N) -> int {
+    auto it = plan_idx.find(N);
+    if (it != plan_idx.end()) return it->second;
+    FftPlan p;
+    int idx = -1;
+    if (fft_plan_for(ctx, N, P, &p) == 0 || bs_plan_for(ctx, N, &p) == 0) {
+      idx = (int)plans.size();
+      plans.push_back(p);
+    }
+    plan_idx[N] = idx;
+    return idx;
+  };
+  for (int i = 0; i < n; ++i) {
+    ImgDesc& d = D[i];
+    if ((rc = describe(ctx, cfg, c.imgs->hw[2 * i], c.imgs->hw[2 * i + 1], d))) return rc;
+    d.rgb_off = c.imgs->img_off[i];
+    if (c.full) {
+      d.row = pack->row[i];
+      d.col = pack->col[i];
+      d.k = pack->k[i];
+      d.local_id = pack->local_id[i];
+      if (d.k < 1 || d.k > d.T || d.k > S)
+        return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": k out of range (FE:429-435)");
+      if (d.row < 0 || d.row >= pack->n_rows || d.col < 0 || d.col + d.k > S)
+        return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": packed span outside (rows, S)");
+    }
+    d.plan_w = plan_of(d.W);
+    d.plan_h = plan_of(d.H);
+    d.bs = (d.plan_w >= 0 && plans[d.plan_w].kind == 1 ? 1 : 0) | (d.plan_h >= 0 && plans[d.plan_h].kind == 1 ? 2 : 0);
+    d.tperm = ctx->opt.tperm && row_route(d) == Route::kGemm && col_route(d) == Route::kGemm;
+    // band layout: rows on k_rows512pk (Kw = 448) and columns on k_cols512b (Kh = 448)
+    d.tband = ctx->opt.cols512b && ctx->opt.rows_kernel == 4 && cfg->max_patch_w == 32 && cfg->max_patch_h == 32 &&
+              d.H == 512 && d.W == 512 && d.Kh == 448 && d.Kw == 448 && row_route(d) == Route::kFft &&
+              col_route(d) == Route::kFft && plans[d.plan_w].spec == 1 && plans[d.plan_h].spec == 1;
+    // packed encodes of band images: item-major token staging (stage_pos; the
+    // staging is internal there, while dctae_spectrum_tokens hands it out in flat order)
+    if (c.full && d.tband) d.tband |= 2;
+  }
+  if (c.full)
+    for (int r = 0; r < pack->n_rows; ++r)
+      if (pack->row_len[r] < 0 || pack->row_len[r] > S) return fail(ctx, DCTAE_EINVAL, "row_len out of range");
+  return 0;
+}
+
+// planner stage 4: the lists of one chunk job, an image's row pass and column
+// pass at a time, then commit() serialises them
+struct JobLists {
+  dctae_ctx* ctx;
+  const dctae_fe_cfg* cfg;
+  const std::vector<FftPlan>& plans;
+  float* ws;
+  ChunkJob& j;
+  std::vector<GemmProblem>& probs;   // the call's; the job's start at p0
+  const size_t p0;
+  const int rows_cap = cfg->patch_size * std::max(cfg->max_patch_h, cfg->max_patch_w);
+  std::vector<TileRef> rt, ct, ft;
+  std::vector<int2> fr[kVariants], br[4], ipt, epi;
+  std::vector<int4> fc[kVariants], bc[4];
+  std::vector<int32_t> fold, pc, pb;
+  int pc_qw = 0;
+  bool pc_ok = cfg->max_patch_h <= 32;   // k_fft_cols7 keeps Kh <= 448 rows
+
+  uint32_t* amax(int li) const { return reinterpret_cast<uint32_t*>(ws + j.amax_off) + 2 * li; }
+
+  // the row pass of image d (local index li): T from the RGB image
+  int rows(const ImgDesc& d, int li) {
+    const Route route = row_route(d);
+    if (route == Route::kBluestein) {
+      const int L = plans[d.plan_w].bs_L, rpb = bs_rows_per_block(L);
+      for (int y0 = 0; y0 < d.H; y0 += rpb) br[bs_lidx(L)].push_back(make_int2(li, y0));
+      return 0;
+    }
+    if (route == Route::kFft) {
+      const FftPlan& p = plans[d.plan_w];
+      for (int y0 = 0; y0 < d.H; y0 += p.rows_per_block) fr[p.spec].push_back(make_int2(li, y0));
+      if (p.spec)
+        j.row_tab[p.spec] = {p.tw_off, p.post_off};
+      else
+        j.lds_rows = std::max<size_t>(j.lds_rows, (size_t)2 * p.rows_per_block * 3 * (2 * p.M + 1) * 4);
+      return 0;
+    }
+    // T[c][y][kx] = sum_x CW[kx][x] * IPT[c][y][x], folded: even kx over
+    // IPT[x] + IPT[W-1-x], odd kx over IPT[x] - IPT[W-1-x] (half the flops)
+    const bool gemm_cols = col_route(d) == Route::kGemm;
+    const size_t q0 = probs.size();
+    for (int par = 0; par < 2; ++par) {
+      const int M = par ? d.Kw / 2 : (d.Kw + 1) / 2, K = par ? d.W / 2 : (d.W + 1) / 2;
+      if (M == 0) continue;
+      const float* CW;
+      if (int rc = dct_matrix(ctx, d.W, std::min(d.W, rows_cap), &CW, par)) return rc;
+      // A: the folded IPT (k_rgb_to_ipt), u at x < ceil(W/2), v after it; B:
+      // the half DCT matrix (shared by the channels).  T rows y are the GEMM
+      // rows, so a wave's stores run along kx (the accumulator's lane-fast
+      // dimension; with the roles swapped they strided by Kw floats)
+      // parity-planar T (tperm: the columns are GEMMs too): each parity's
+      // outputs are contiguous runs (interleaved stores made every line
+      // twice-written: 4.4 GB of writes for 2.7 GB of T on config 4)
+      GemmProblem g = d.tperm ? gemm(ws + d.ws_p + (par ? (d.W + 1) / 2 : 0), (int64_t)d.H * d.W, d.W, 1, CW, 0,
+                                     K, 1, ws + d.ws_t + (par ? (d.Kw + 1) / 2 : 0), (int64_t)d.Kw * d.H, d.Kw,
+                                     1, d.H, M, K, 3)
+                              : gemm(ws + d.ws_p + (par ? (d.W + 1) / 2 : 0), (int64_t)d.H * d.W, d.W, 1, CW, 0,
+                                     K, 1, ws + d.ws_t + par, (int64_t)d.Kw * d.H, d.Kw, 2, d.H, M, K, 3);
+      attach_x3(ctx, g);
+      g.amax = amax(li);                              // k_rgb_to_ipt's |max| of the folded IPT
+      g.omax = gemm_cols ? amax(li) + 1 : nullptr;    // T's |max| for the column GEMM
+      g.pad2 = li;                                    // k_rows_fused: the image and the parity
+      g.pad3 = par;
+      probs.push_back(g);
+    }
+    // k_rows_fused (colour transform + folds + row GEMM in one pass) for the
+    // tperm images whose parity matrices are cached pre-split (both forms:
+    // the fix-up runs the bf16 one) and fit its 256 output columns
+    bool fz = ctx->opt.rows_fused && d.tperm && probs.size() == q0 + 2;   // both parities, consecutive
+    for (size_t q = q0; q < probs.size(); ++q) fz = fz && probs[q].Xh && probs[q].N <= fused_max_n();
+    if (fz) {
+      for (int rb = 0; rb * fused_pairs_per_block() < (d.H + 1) / 2; ++rb) ft.push_back(TileRef{(int)(q0 - p0), rb});
+      return 0;
+    }
+    for (size_t q = q0; q < probs.size(); ++q) add_tiles(rt, (int)(q - p0), probs[q]);
+    // k_rgb_to_ipt's (x, y)-mirrored pixel groups of this image
+    const int64_t ng = (int64_t)(gemm_cols ? (d.H + 1) / 2 : d.H) * ((d.W + 1) / 2);
+    for (int64_t g0 = 0; g0 < ng; g0 += rgb_to_ipt_groups_per_block()) ipt.push_back(make_int2(li, (int)g0));
+    return 0;
+  }
+
+  // the column pass of image d: tokens from T (through Y and the tile epilogue on the GEMM and Bluestein routes)
+  int cols(const ImgDesc& d, int li) {
+    if (regions_of(d).y)   // Y in the workspace: the tile epilogue's (tile row, channel) blocks
+      for (int h = 0; h < d.qh; ++h)
+        for (int c = 0; c < 3; ++c) epi.push_back(make_int2(li, 3 * h + c));
+    const Route route = col_route(d);
+    if (route == Route::kBluestein) {
+      const int L = plans[d.plan_h].bs_L, cpb = bs_cols_per_block(L);
+      for (int c = 0; c < 3; ++c)
+        for (int kx0 = 0; kx0 < d.Kw; kx0 += cpb) bc[bs_lidx(L)].push_back(make_int4(li, c, kx0, 0));
+    } else if (route == Route::kBand) {
+      pb.push_back(li);
+      j.col_tab[1] = {plans[d.plan_h].tw_off, plans[d.plan_h].post_off};
+    } else if (route == Route::kFft) {
+      const FftPlan& p = plans[d.plan_h];
+      // generic kernel: one tile column per block; specialised: groups of
+      // up to 16 adjacent tile columns walked by one block
+      const int G = 1;
+      for (int c = 0; c < 3; ++c)
+        for (int w = 0; w < d.qw; w += G) fc[p.spec].push_back(make_int4(li, c, w, std::min(G, d.qw - w)));
+      if (p.spec == 1) {
+        pc_ok = pc_ok && (pc.empty() || d.qw == pc_qw);
+        pc_qw = d.qw;
+        pc.push_back(li);
+      }
+      if (p.spec)
+        j.col_tab[p.spec] = {p.tw_off, p.post_off};
+      else
+        j.lds_cols = std::max<size_t>(j.lds_cols, (size_t)2 * 2 * p.M * cfg->patch_size * 4);
+    } else {
+      // Y[c][ky][kx] = sum_y CH[ky][y] * T[c][y][kx], folded along y as the rows
+      for (int par = 0; par < 2; ++par) {
+        const int M = par ? d.Kh / 2 : (d.Kh + 1) / 2, K = par ? d.H / 2 : (d.H + 1) / 2;
+        if (M == 0) continue;
+        const float* CH;
+        if (int rc = dct_matrix(ctx, d.H, std::min(d.H, rows_cap), &CH, par)) return rc;
+        // B: T folded along y (by the row GEMM of the y-folded IPT, or in place by
+        // k_fold_t after FFT rows): u in rows m < ceil(H/2), v[m] in row H-1-m
+        GemmProblem g = gemm(CH, 0, K, 1, ws + d.ws_t + (par ? (int64_t)(d.H - 1) * d.Kw : 0),
+                             (int64_t)d.Kw * d.H, 1, par ? -(int64_t)d.Kw : d.Kw,
+                             ws + d.ws_y + (int64_t)par * d.Kw, (int64_t)d.Kh * d.Kw, 2 * (int64_t)d.Kw, 1, M,
+                             d.Kw, K, 3);
+        attach_x3(ctx, g);
+        g.amax = amax(li) + 1;   // T's |max| (row GEMM / k_fold_t)
+        add_tiles(ct, (int)(probs.size() - p0), g);
+        probs.push_back(g);
+      }
+      if (row_route(d) != Route::kGemm) {
+        fold.push_back(li);
+        j.fold_max_hw = std::max<int64_t>(j.fold_max_hw, (int64_t)d.H * d.W);
+      }
+    }
+    return 0;
+  }
+
+  // the job's lists into the plan; the order of the adds is the order of the plan's bytes
+  void commit(PlanBuf& out, const ImgDesc* D) {
+    const GemmProblem* gp = probs.data() + p0;
+    const int n_gp = (int)(probs.size() - p0);
+    j.desc = {out.add(D, j.i1 - j.i0), j.i1 - j.i0};
+    // k_gemm_h2 when every GEMM of the job has its shared matrix pre-split
+    j.h2 = ctx->opt.gemm_x3 && ctx->opt.gemm_h2 && n_gp > 0;
+    for (int q = 0; q < n_gp; ++q) j.h2 = j.h2 && gp[q].Xh != nullptr;
+    j.gp = {out.add(gp, n_gp), n_gp};
+    if (ctx->opt.xcd_order) {
+      xcd_deal_tiles(rt, gp, 1);
+      xcd_deal_tiles(ct, gp, 2);
+      xcd_deal_tiles(ft, gp, 1);   // an image's blocks on one XCD: its two matrices in one L2
+      for (int v = 1; v < kVariants; ++v) xcd_deal_col_blocks(fc[v]);
+    }
+    j.rows_t = out.add(rt);
+    j.fused_t = out.add(ft);
+    j.cols_t = out.add(ct);
+    for (int v = 0; v < kVariants; ++v) {
+      j.fr[v] = out.add(fr[v]);
+      j.fc[v] = out.add(fc[v]);
+    }
+    j.ipt = out.add(ipt);
+    j.fold = out.add(fold);
+    for (int l = 0; l < 4; ++l) {
+      j.br[l] = out.add(br[l]);
+      j.bc[l] = out.add(bc[l]);
+    }
+    // all spec-1 column items of the job in one persistent launch, when their qw agree
+    j.n_pc = (pc_ok && (int)pc.size() * 3 * pc_qw == (int)fc[1].size()) ? (int)pc.size() : 0;
+    j.pc_qw = pc_qw;
+    j.pc = out.add(pc);
+    j.pb = out.add(pb);
+    j.epi = out.add(epi);
+  }
+};
+
+// The encode engine.  Full mode (pack != NULL): packed DCTPatches outputs.
+// Token mode (pack == NULL): spectrum tokens in flat order (tokens_dev /
+// scores_dev at tok_off).  Per image the row DCT (length W) and the column
+// DCT (length H) each run on the FFT kernels when the length has a plan, else
+// on the MFMA GEMM; the intermediate T[c][y][kx] (3, H, Kw) is shared.
+static int build_encode_plan(OrderedCall& oc, const EncCall& c, EncPlan& E) {
+  dctae_ctx* ctx = oc.ctx;
+  int rc;
+  // 1. describe and validate the images
+  EncImages im;
+  if ((rc = describe_images(ctx, c, im))) return rc;
+  std::vector<ImgDesc>& D = im.D;
+  const int n = (int)D.size();
+  // 2. cut chunks and lay out the workspace (dctae_enc_layout.h); tokens in image order
+  const WsLayout wl = lay_out_workspace(D.data(), n, ctx->opt);
+  E.ws_need = wl.ws_need;
+  for (const JobRange& r : wl.jobs) {
+    ChunkJob j{};
+    j.i0 = r.i0, j.i1 = r.i1, j.amax_off = r.amax_off, j.max_T = 1;
+    for (int i = j.i0; i < j.i1; ++i) {
+      D[i].tok_off = c.full ? E.n_tok : c.tok_off_user[i];
+      E.n_tok += D[i].T;
+      j.max_T = std::max(j.max_T, D[i].T);
+    }
+    E.max_T = std::max(E.max_T, j.max_T);
+    E.jobs.push_back(j);
+  }
+  E.n_img = n;
+  E.uniform = true;
+  for (int i = 1; i < n; ++i) E.uniform = E.uniform && D[i].H == D[0].H && D[i].W == D[0].W;
+  // 3. size the scratch: both buffers where the plan is built (token_sinks carves the staging)
+  E.stage = StageLayout(E.n_tok, c.ncb, c.cfg->patch_size * c.cfg->patch_size, c.want_norm, c.want_raw && c.full);
+  uint8_t* st;
+  if ((rc = oc.scratch(kWs, std::max<size_t>(E.ws_need, 256), &E.ws)) ||
+      (rc = oc.scratch(kStage, std::max<size_t>(E.stage.need, 256), &st)))
+    return rc;
+  // 4. build each job's lists
+  std::vector<GemmProblem> probs;
+  for (ChunkJob& j : E.jobs) {
+    JobLists b{ctx, c.cfg, im.plans, E.ws, j, probs, probs.size()};
+    for (int i = j.i0; i < j.i1; ++i)
+      if ((rc = b.rows(D[i], i - j.i0)) || (rc = b.cols(D[i], i - j.i0))) return rc;
+    b.commit(E.pb, D.data() + j.i0);
+  }
+  // 5. serialise what the jobs share
+  E.plans = E.pb.add(im.plans);
+  E.all_desc = E.pb.add(D);
+  E.any_pad = false;
+  if (c.full) {
+    if (c.pack->n_rows > 0) E.rowlen = {E.pb.add(c.pack->row_len, c.pack->n_rows), c.pack->n_rows};
+    for (int r = 0; r < c.pack->n_rows; ++r) E.any_pad = E.any_pad || c.pack->row_len[r] < c.cfg->max_seq_len;
+  }
+  return 0;
+}
+
 // the call's plan: the cached one, or a new one that replaces it
 static int encode_plan(OrderedCall& oc, const EncCall& c, EncPlan** out) {
   dctae_ctx* ctx = oc.ctx;
@@ -482,7 +427,7 @@ static int encode_plan(OrderedCall& oc, const EncCall& c, EncPlan** out) {
   if (!ctx->enc_plan || ctx->enc_plan->ws != ws || key != ctx->enc_key) {
     EncPlan* E = new EncPlan();
     E->id = ++ctx->plan_counter;
-    rc = build_encode_plan(oc, c.cfg, c.imgs, c.pack, c.full, c.ncb, c.want_raw, c.want_norm, c.tok_off_user, *E);
+    rc = build_encode_plan(oc, c, *E);
     if (rc) {
       delete E;
       return rc;
@@ -501,16 +446,8 @@ void dctae::drop_encode_plan(dctae_ctx* ctx) {
 }
 
 static PackSinks pack_sinks(const dctae_packed_out* out) {
-  PackSinks ps{};
-  ps.codes = out->codes_dev;
-  ps.pos = out->positions_dev;
-  ps.ch = out->channels_dev;
-  ps.ids = out->image_ids_dev;
-  ps.patches = out->patches_dev;
-  ps.raw = out->raw_patches_dev;
-  ps.scores = out->scores_dev;
-  ps.key_pad = out->key_pad_dev;
-  return ps;
+  return PackSinks{out->codes_dev,   out->positions_dev,   out->channels_dev, out->image_ids_dev,
+                   out->patches_dev, out->raw_patches_dev, out->scores_dev,   out->key_pad_dev};
 }
 
 // token staging for the whole call (flat token order, global offsets)
@@ -521,24 +458,12 @@ static int token_sinks(OrderedCall& oc, const EncCall& c, const EncPlan& E, Toke
     sk.raw = c.tokens_dev;
     return 0;
   }
-  const int PP = c.cfg->patch_size * c.cfg->patch_size;
-  const int64_t nt = E.n_tok;
   uint8_t* st;
-  if (int rc = oc.scratch(kStage, std::max<size_t>(E.st_need, 256), &st)) return rc;
-  sk.scores = (float*)st;
-  st += ((nt * 4 + 255) & ~255ll);
-  if (c.ncb) {
-    sk.codes = (uint16_t*)st;
-    st += ((nt * 2 * c.ncb + 255) & ~255ll);
-  }
-  if (c.want_norm) {
-    sk.norm = (float*)st;
-    st += nt * 4 * PP;
-  }
-  if (c.out->raw_patches_dev) {
-    sk.raw = (float*)st;
-    st += nt * 4 * PP;
-  }
+  if (int rc = oc.scratch(kStage, std::max<size_t>(E.stage.need, 256), &st)) return rc;
+  sk.scores = (float*)(st + E.stage.scores);
+  if (c.ncb) sk.codes = (uint16_t*)(st + E.stage.codes);
+  if (c.want_norm) sk.norm = (float*)(st + E.stage.norm);
+  if (c.want_raw) sk.raw = (float*)(st + E.stage.raw);
   return 0;
 }
 
@@ -590,102 +515,108 @@ struct EncLaunch {
   EncParams eps;             // the pack's parameters
   PackSinks ps;
 
-  void gemm(const ChunkJob& j, size_t tiles_off, int n_tiles, hipStream_t st, int share) const {
+  void gemm(const ChunkJob& j, const PlanList<TileRef>& tiles, hipStream_t st, int share) const {
     if (j.h2)
-      launch_gemm_h2((const GemmProblem*)(pd + j.gp_off), (const TileRef*)(pd + tiles_off), n_tiles, st, share,
-                     ctx->opt.gemm_dma != 0, ctx->opt.cols_dma != 0);
+      launch_gemm_h2(j.gp.at(pd), tiles.at(pd), tiles.n, st, share, ctx->opt.gemm_dma != 0, ctx->opt.cols_dma != 0);
     else
-      ctx_gemm(ctx, 3, (const GemmProblem*)(pd + j.gp_off), (const TileRef*)(pd + tiles_off), n_tiles, st, share);
+      ctx_gemm(ctx, 3, j.gp.at(pd), tiles.at(pd), tiles.n, st, share);
+  }
+
+  // The FFT kernel families that are launched on part of a list too: blocks /
+  // items [a, a + m) of the job's list on a stream, one spelling each.
+  void rows_spec(const ChunkJob& j, int v, int a, int m, hipStream_t st) const {
+    Timer t(ctx, st, "fft_rows");
+    launch_fft_rows_spec(v, j.desc.at(pd), j.fr[v].at(pd) + a, m, imgs->rgb_dev, E.ws,
+                         ctx->fft_tab + j.row_tab[v].tw_off, ctx->fft_tab + j.row_tab[v].post_off, ctx->cm, st);
+  }
+  void rows512(const ChunkJob& j, int a, int m, hipStream_t st) const {
+    Timer t(ctx, st, "fft_rows");
+    launch_rows512(j.desc.at(pd), j.fr[1].at(pd) + a, m, imgs->rgb_dev, E.ws, ctx->fft_tab + j.row_tab[1].tw_off,
+                   ctx->fft_tab + j.row_tab[1].post_off, ctx->cm, st);
+  }
+  void cols_band(const ChunkJob& j, int a, int m, hipStream_t st, bool allow_wide = true) const {
+    Timer t(ctx, st, "fft_cols");
+    launch_cols512b(j.desc.at(pd), j.pb.at(pd) + a, m, E.ws, ctx->fft_tab + j.col_tab[1].tw_off,
+                    ctx->fft_tab + j.col_tab[1].post_off, epj, skc, st, allow_wide && ctx->opt.cols_wide != 0);
+  }
+  // (k_fft_cols7's persistent list serves the whole spec-1 list: a job that has one is never split)
+  void cols_spec(const ChunkJob& j, int v, int a, int m, hipStream_t st) const {
+    Timer t(ctx, st, "fft_cols");
+    launch_fft_cols_spec(v, j.desc.at(pd), j.fc[v].at(pd) + a, m, E.ws, ctx->fft_tab + j.col_tab[v].tw_off,
+                         ctx->fft_tab + j.col_tab[v].post_off, epj, skc, st,
+                         v == 1 && j.n_pc ? j.pc.at(pd) : nullptr, v == 1 ? j.n_pc : 0, j.pc_qw);
   }
 
   // row half of a chunk job on a stream
   void do_rows(const ChunkJob& j, hipStream_t st) const {
-    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
+    const ImgDesc* dd = j.desc.at(pd);
+    const int nj = j.i1 - j.i0;
     uint32_t* amax = reinterpret_cast<uint32_t*>(E.ws + j.amax_off);
-    if (j.h2 || j.any_fused) hipMemsetAsync(amax, 0, 12 * (size_t)(j.i1 - j.i0) + 36, st);   // errors surface at hipGetLastError
-    if (j.any_fused) {
-      int* flags = reinterpret_cast<int*>(amax + 2 * (j.i1 - j.i0));
-      {
-        Timer t(ctx, st, "rows_fused");
-        launch_rows_fused((const GemmProblem*)(pd + j.gp_off), (const TileRef*)(pd + j.fused_t_off), j.n_fused_tiles,
-                          dd, imgs->rgb_dev, ctx->cm, amax, flags, j.i1 - j.i0, st, false);
+    if (j.h2 || j.fused_t.n) hipMemsetAsync(amax, 0, 12 * (size_t)nj + 36, st);   // errors surface at hipGetLastError
+    if (j.fused_t.n) {
+      int* flags = reinterpret_cast<int*>(amax + 2 * nj);
+      for (int fixup = 0; fixup < 2; ++fixup) {
+        Timer t(ctx, st, fixup ? "rows_fixup" : "rows_fused");
+        launch_rows_fused(j.gp.at(pd), j.fused_t.at(pd), j.fused_t.n, dd, imgs->rgb_dev, ctx->cm, amax, flags, nj, st,
+                          fixup != 0);
       }
-      Timer t(ctx, st, "rows_fixup");
-      launch_rows_fused((const GemmProblem*)(pd + j.gp_off), (const TileRef*)(pd + j.fused_t_off), j.n_fused_tiles, dd,
-                        imgs->rgb_dev, ctx->cm, amax, flags, j.i1 - j.i0, st, true);
     }
-    if (j.any_gemm_rows) {
+    if (j.rows_t.n) {
       {
         Timer t(ctx, st, "rgb_to_ipt");
-        launch_rgb_to_ipt(dd, (const int2*)(pd + j.ipt_off), j.n_ipt, imgs->rgb_dev, E.ws, ctx->cm,
-                          j.h2 ? amax : nullptr, st);
+        launch_rgb_to_ipt(dd, j.ipt.at(pd), j.ipt.n, imgs->rgb_dev, E.ws, ctx->cm, j.h2 ? amax : nullptr, st);
       }
       Timer t(ctx, st, "gemm_rows");
-      gemm(j, j.rows_t_off, j.n_rows_tiles, st, 1);
+      gemm(j, j.rows_t, st, 1);
     }
     for (int l = 0; l < 4; ++l)
-      if (j.n_br[l]) {
+      if (j.br[l].n) {
         Timer t(ctx, st, "bs_rows");
-        launch_bs_rows(kBsL[l], dd, plans_d, (const int2*)(pd + j.br_off[l]), j.n_br[l], imgs->rgb_dev, E.ws,
-                       ctx->fft_tab, ctx->cm, st, ctx->opt.bs_ablate);
+        launch_bs_rows(kBsL[l], dd, plans_d, j.br[l].at(pd), j.br[l].n, imgs->rgb_dev, E.ws, ctx->fft_tab, ctx->cm, st,
+                       ctx->opt.bs_ablate);
       }
-    if (j.n_fr[0]) {
+    if (j.fr[0].n) {
       Timer t(ctx, st, "fft_rows");
-      launch_fft_rows(dd, plans_d, (const int2*)(pd + j.fr_off[0]), j.n_fr[0], j.lds_rows, imgs->rgb_dev, E.ws,
-                      ctx->fft_tab, ctx->cm, st);
+      launch_fft_rows(dd, plans_d, j.fr[0].at(pd), j.fr[0].n, j.lds_rows, imgs->rgb_dev, E.ws, ctx->fft_tab, ctx->cm,
+                      st);
     }
     for (int v = 1; v < kVariants; ++v)
-      if (j.n_fr[v]) {
-        Timer t(ctx, st, "fft_rows");
+      if (j.fr[v].n) {
         if (v == 1 && ctx->opt.rows_kernel == 4 && cfg->max_patch_w == 32)
-          launch_rows512(dd, (const int2*)(pd + j.fr_off[v]), j.n_fr[v], imgs->rgb_dev, E.ws,
-                         ctx->fft_tab + j.tw_off[v], ctx->fft_tab + j.post_off_r[v], ctx->cm, st);
+          rows512(j, 0, j.fr[v].n, st);
         else
-          launch_fft_rows_spec(v, dd, (const int2*)(pd + j.fr_off[v]), j.n_fr[v], imgs->rgb_dev, E.ws,
-                               ctx->fft_tab + j.tw_off[v], ctx->fft_tab + j.post_off_r[v], ctx->cm, st);
+          rows_spec(j, v, 0, j.fr[v].n, st);
       }
   }
 
   // column half of a chunk job on a stream
   void do_cols(const ChunkJob& j, hipStream_t st) const {
-    const int nj = j.i1 - j.i0;
-    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
-    if (j.any_gemm_cols) {
-      if (j.fold_t) {
+    const ImgDesc* dd = j.desc.at(pd);
+    if (j.cols_t.n) {
+      if (j.fold.n) {
         Timer t(ctx, st, "fold_t");
-        launch_fold_t(dd, (const int32_t*)(pd + j.fold_off), j.n_fold, j.fold_max_hw, E.ws,
+        launch_fold_t(dd, j.fold.at(pd), j.fold.n, j.fold_max_hw, E.ws,
                       j.h2 ? reinterpret_cast<uint32_t*>(E.ws + j.amax_off) : nullptr, st);
       }
       Timer t(ctx, st, "gemm_cols");
-      gemm(j, j.cols_t_off, j.n_cols_tiles, st, 2);
+      gemm(j, j.cols_t, st, 2);
     }
     for (int l = 0; l < 4; ++l)
-      if (j.n_bc[l]) {
+      if (j.bc[l].n) {
         Timer t(ctx, st, "bs_cols");
-        launch_bs_cols(kBsL[l], dd, plans_d, (const int4*)(pd + j.bc_off[l]), j.n_bc[l], E.ws, ctx->fft_tab, st,
-                       ctx->opt.bs_ablate);
+        launch_bs_cols(kBsL[l], dd, plans_d, j.bc[l].at(pd), j.bc[l].n, E.ws, ctx->fft_tab, st, ctx->opt.bs_ablate);
       }
-    if (j.any_gemm_cols || j.any_bs_cols) {
+    if (j.epi.n) {   // the images with Y in the workspace: columns on the GEMM or Bluestein
       Timer t(ctx, st, "tile_epilogue");
-      launch_tile_epilogue(dd, nj, j.max_T, E.ws, epj, skc, st, (const int2*)(pd + j.epi_off), j.n_epi);
+      launch_tile_epilogue(dd, j.i1 - j.i0, j.max_T, E.ws, epj, skc, st, j.epi.at(pd), j.epi.n);
     }
-    if (j.n_fc[0]) {
+    if (j.fc[0].n) {
       Timer t(ctx, st, "fft_cols");
-      launch_fft_cols(dd, plans_d, (const int4*)(pd + j.fc_off[0]), j.n_fc[0], j.lds_cols, E.ws, ctx->fft_tab,
-                      epj, skc, st);
+      launch_fft_cols(dd, plans_d, j.fc[0].at(pd), j.fc[0].n, j.lds_cols, E.ws, ctx->fft_tab, epj, skc, st);
     }
-    if (j.n_pb) {
-      Timer t(ctx, st, "fft_cols");
-      launch_cols512b(dd, (const int*)(pd + j.pb_off), j.n_pb, E.ws, ctx->fft_tab + j.tw_off_c[1],
-                      ctx->fft_tab + j.post_off_c[1], epj, skc, st, ctx->opt.cols_wide != 0);
-    }
+    if (j.pb.n) cols_band(j, 0, j.pb.n, st);
     for (int v = 1; v < kVariants; ++v)
-      if (j.n_fc[v]) {
-        Timer t(ctx, st, "fft_cols");
-        launch_fft_cols_spec(v, dd, (const int4*)(pd + j.fc_off[v]), j.n_fc[v], E.ws, ctx->fft_tab + j.tw_off_c[v],
-                             ctx->fft_tab + j.post_off_c[v], epj, skc, st,
-                             v == 1 && j.n_pc ? (const int*)(pd + j.pc_off) : nullptr, v == 1 ? j.n_pc : 0, j.pc_qw);
-      }
+      if (j.fc[v].n) cols_spec(j, v, 0, j.fc[v].n, st);
   }
 
   // sort / pack of images [a, a + m) on a stream
@@ -698,45 +629,31 @@ struct EncLaunch {
   int halves_variant() const {
     if (E.jobs.size() != 1 || !E.uniform || E.n_img < 32) return 0;
     const ChunkJob& j = E.jobs[0];
-    bool ok = !j.any_gemm_rows && !j.any_gemm_cols && !j.any_bs_cols && j.n_pb == 0 && j.n_pc == 0 && j.n_fr[0] == 0 &&
-              j.n_fc[0] == 0;
-    for (int l = 0; l < 4; ++l) ok = ok && !j.n_br[l] && !j.n_bc[l];
+    bool ok = !j.rows_t.n && !j.cols_t.n && j.pb.n == 0 && j.n_pc == 0 && j.fr[0].n == 0 && j.fc[0].n == 0;
+    for (int l = 0; l < 4; ++l) ok = ok && !j.br[l].n && !j.bc[l].n;
     int vv = -1;
     for (int v = 1; v < kVariants; ++v)
-      if (j.n_fr[v] || j.n_fc[v]) {
-        if (vv < 0 && j.n_fr[v] && j.n_fc[v]) vv = v;
+      if (j.fr[v].n || j.fc[v].n) {
+        if (vv < 0 && j.fr[v].n && j.fc[v].n) vv = v;
         else ok = false;
       }
-    return ok && vv >= 2 && j.n_fr[vv] % E.n_img == 0 && j.n_fc[vv] % E.n_img == 0 ? vv : 0;
+    return ok && vv >= 2 && j.fr[vv].n % E.n_img == 0 && j.fc[vv].n % E.n_img == 0 ? vv : 0;
   }
 
   // the halves schedule on plan kernel variant hv; *sorted0 = the images it packed
   int run_halves(int hv, SideStream& side, int* sorted0) const {
     const ChunkJob& j = E.jobs[0];
-    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
     const int n_img = E.n_img, h = n_img / 2;
-    const int rpi = j.n_fr[hv] / n_img, cpi = j.n_fc[hv] / n_img;   // blocks / items per image (image-major lists)
-    const int2* rl = (const int2*)(pd + j.fr_off[hv]);
-    const int4* cl = (const int4*)(pd + j.fc_off[hv]);
-    auto rows = [&](int a, int m, hipStream_t st) {
-      Timer t(ctx, st, "fft_rows");
-      launch_fft_rows_spec(hv, dd, rl + (size_t)a * rpi, m * rpi, imgs->rgb_dev, E.ws, ctx->fft_tab + j.tw_off[hv],
-                           ctx->fft_tab + j.post_off_r[hv], ctx->cm, st);
-    };
-    auto cols = [&](int a, int m, hipStream_t st) {
-      Timer t(ctx, st, "fft_cols");
-      launch_fft_cols_spec(hv, dd, cl + (size_t)a * cpi, m * cpi, E.ws, ctx->fft_tab + j.tw_off_c[hv],
-                           ctx->fft_tab + j.post_off_c[hv], epj, skc, st, nullptr, 0, 0);
-    };
-    rows(0, h, s);
+    const int rpi = j.fr[hv].n / n_img, cpi = j.fc[hv].n / n_img;   // blocks / items per image (image-major lists)
+    rows_spec(j, hv, 0, h * rpi, s);
     if (int rc = side.fork(s)) return rc;
-    cols(0, h, ctx->side);
+    cols_spec(j, hv, 0, h * cpi, ctx->side);
     {
       Timer t(ctx, ctx->side, "sort_pack");
       sort_pack(0, h, ctx->side);
     }
-    rows(h, n_img - h, s);
-    cols(h, n_img - h, s);
+    rows_spec(j, hv, h * rpi, (n_img - h) * rpi, s);
+    cols_spec(j, hv, h * cpi, (n_img - h) * cpi, s);
     *sorted0 = h;
     return 0;
   }
@@ -745,48 +662,27 @@ struct EncLaunch {
   // first half's sort / pack on the side stream while the second half's
   // columns run (the sort is latency-bound, the column kernel issue-bound)
   int run_split_cols(const ChunkJob& j, SideStream& side, int* sorted0) const {
-    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
-    const int* list = (const int*)(pd + j.pb_off);
-    const int h = j.n_pb / 2;
-    {
-      Timer t(ctx, s, "fft_cols");
-      launch_cols512b(dd, list, h, E.ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1], epj, skc, s,
-                      ctx->opt.cols_wide != 0);
-    }
+    const int h = j.pb.n / 2;
+    cols_band(j, 0, h, s);
     if (int rc = side.fork(s)) return rc;
     sort_pack(0, h, ctx->side);
-    {
-      Timer t(ctx, s, "fft_cols");
-      launch_cols512b(dd, list + h, j.n_pb - h, E.ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1],
-                      epj, skc, s, ctx->opt.cols_wide != 0);
-    }
+    cols_band(j, h, j.pb.n - h, s);
     *sorted0 = h;
     return 0;
   }
 
 #ifdef DCTAE_PROFILING
   bool gate_applies() const {
-    return ctx->opt.gate && E.jobs.size() == 1 && E.n_img >= 2 && E.jobs[0].n_pb == E.n_img &&
-           E.jobs[0].n_fr[1] % E.n_img == 0 && ctx->opt.rows_kernel == 4;
+    return ctx->opt.gate && E.jobs.size() == 1 && E.n_img >= 2 && E.jobs[0].pb.n == E.n_img &&
+           E.jobs[0].fr[1].n % E.n_img == 0 && ctx->opt.rows_kernel == 4;
   }
 
   // the profiling gate (Options::gate): part of the band path; *sorted0 = the images to leave unpacked
   int run_gate(SideStream& side, int* sorted0) const {
     const ChunkJob& j = E.jobs[0];
-    const ImgDesc* dd = (const ImgDesc*)(pd + j.desc_off);
-    const int n_img = E.n_img, h = n_img / 2, rpi = j.n_fr[1] / n_img;
-    const int2* rl = (const int2*)(pd + j.fr_off[1]);
-    const int* cl = (const int*)(pd + j.pb_off);
-    auto rows = [&](int a, int m, hipStream_t st) {
-      Timer t(ctx, st, "fft_rows");
-      launch_rows512(dd, rl + (size_t)a * rpi, m * rpi, imgs->rgb_dev, E.ws, ctx->fft_tab + j.tw_off[1],
-                     ctx->fft_tab + j.post_off_r[1], ctx->cm, st);
-    };
-    auto cols = [&](int a, int m, hipStream_t st) {
-      Timer t(ctx, st, "fft_cols");
-      launch_cols512b(dd, cl + a, m, E.ws, ctx->fft_tab + j.tw_off_c[1], ctx->fft_tab + j.post_off_c[1], epj, skc,
-                      st, false);
-    };
+    const int n_img = E.n_img, h = n_img / 2, rpi = j.fr[1].n / n_img;
+    auto rows = [&](int a, int m, hipStream_t st) { rows512(j, a * rpi, m * rpi, st); };
+    auto cols = [&](int a, int m, hipStream_t st) { cols_band(j, a, m, st, false); };
     const int64_t gate = ctx->opt.gate;
     if (int rc = side.ensure()) return rc;
     switch (gate) {
@@ -810,14 +706,14 @@ struct EncLaunch {
 #endif
 };
 
-static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
-                       const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
-                       const dctae_packed_out* out, const int64_t* tok_off_user, float* tokens_dev,
-                       float* scores_dev, hipStream_t s, const float* proj_w = nullptr,
-                       const float* proj_b = nullptr) {
-  EncCall c{cfg, imgs, pack, norm, lfq, out, tok_off_user, tokens_dev, scores_dev, proj_w, proj_b};
+// one encode call on stream s: c holds the entry point's arguments
+static int encode_call(dctae_ctx* ctx, EncCall& c, hipStream_t s) {
   int rc = c.check(ctx);
   if (rc) return rc;
+  const dctae_fe_cfg* cfg = c.cfg;
+  const dctae_norm* norm = c.norm;
+  const dctae_lfq* lfq = c.lfq;
+  const float* proj_w = c.proj_w;
   const bool full = c.full;
   OrderedCall oc(ctx, s);   // before the plan: building it sizes the workspace
   EncPlan* plan;
@@ -830,7 +726,7 @@ static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_imag
 
   EncParams ep = enc_params(cfg, norm, c.want_codes && !proj_w ? lfq : nullptr);
   if (norm && !c.want_norm) ep.thr = norm->thr_dev;
-  EncLaunch L{ctx, cfg, imgs, E, s, pd, (const FftPlan*)(pd + E.plans_off), (const ImgDesc*)(pd + E.all_desc_off)};
+  EncLaunch L{ctx, cfg, c.imgs, E, s, pd, E.plans.at(pd), E.all_desc.at(pd)};
   L.epj = ep;
   if (!full) L.epj.median = nullptr;
   // the pack's parameters (the projection kernel stages raw sign bits: the pack maps them, lfq_index_bits)
@@ -844,12 +740,12 @@ static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_imag
     L.eps.code_neg = (uint32_t)neg;
   }
   if (full) {
-    L.ps = pack_sinks(out);
+    L.ps = pack_sinks(c.out);
     // rows filled to max_seq_len (e.g. one 512^2 image per row) have no pads:
     // the sort kernel writes their key_pad zeros, no k_pad_fill launch
-    if (pack->n_rows > 0 && E.any_pad) {
+    if (c.pack->n_rows > 0 && E.any_pad) {
       Timer t(ctx, s, "pad_fill");
-      launch_pad_fill((const int32_t*)(pd + E.rowlen_off), pack->n_rows, ep, out->key_pad_dev, L.ps, s);
+      launch_pad_fill(E.rowlen.at(pd), c.pack->n_rows, ep, c.out->key_pad_dev, L.ps, s);
     }
   }
   if ((rc = token_sinks(oc, c, E, L.sk))) return rc;
@@ -860,7 +756,7 @@ static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_imag
   SideStream side(ctx);
   const bool two = full && !proj_w;
   const bool split = two && ctx->opt.sort_overlap && E.jobs.size() == 1 && E.n_img >= 64 &&
-                     E.jobs[0].n_pb == E.n_img && E.jobs[0].i0 == 0;
+                     E.jobs[0].pb.n == E.n_img && E.jobs[0].i0 == 0;
   const int hv = two && ctx->opt.halves && !split ? L.halves_variant() : 0;
   if ((split || hv) && (rc = side.ensure())) return rc;
   int sorted0 = 0;   // images [0, sorted0) need no sort / pack on the caller's stream
@@ -891,8 +787,8 @@ static int encode_impl(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_imag
     // the staged tokens are PatchNorm outputs, clamped to [min_val, max_val]
     // (patchnorm.py:163): the fp16 projection's operand bound
     const float xb = ctx->opt.gemm_h2 ? std::max(std::fabs(norm->min_val), std::fabs(norm->max_val)) : 0.0f;
-    launch_lfq_project_in16(L.sk.norm, E.n_tok, PP, proj_w, proj_b, lfq->codebook_dim, lfq->num_codebooks, L.sk.codes,
-                            wsp, s, xb, ctx->opt.lfq_ws != 0);
+    launch_lfq_project_in16(L.sk.norm, E.n_tok, PP, proj_w, c.proj_b, lfq->codebook_dim, lfq->num_codebooks,
+                            L.sk.codes, wsp, s, xb, ctx->opt.lfq_ws != 0);
   }
   if (full && E.n_img > sorted0) {
     Timer t(ctx, s, "sort_pack");
@@ -910,7 +806,9 @@ int dctae_encode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* im
   if (!ctx) return DCTAE_EINVAL;
   if (!pack) return fail(ctx, DCTAE_EINVAL, "packing descriptor is NULL");
   hipSetDevice(ctx->device);
-  return encode_impl(ctx, cfg, imgs, pack, norm, lfq, out, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  EncCall c{};
+  c.cfg = cfg, c.imgs = imgs, c.pack = pack, c.norm = norm, c.lfq = lfq, c.out = out;
+  return encode_call(ctx, c, (hipStream_t)stream);
 }
 
 int dctae_encode_lfq_proj(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
@@ -920,8 +818,10 @@ int dctae_encode_lfq_proj(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_i
   if (!pack) return fail(ctx, DCTAE_EINVAL, "packing descriptor is NULL");
   if (!w_in_dev || !out || !out->codes_dev) return fail(ctx, DCTAE_EINVAL, "project_in weight and codes output required");
   hipSetDevice(ctx->device);
-  return encode_impl(ctx, cfg, imgs, pack, norm, lfq, out, nullptr, nullptr, nullptr, (hipStream_t)stream, w_in_dev,
-                     b_in_dev);
+  EncCall c{};
+  c.cfg = cfg, c.imgs = imgs, c.pack = pack, c.norm = norm, c.lfq = lfq, c.out = out;
+  c.proj_w = w_in_dev, c.proj_b = b_in_dev;
+  return encode_call(ctx, c, (hipStream_t)stream);
 }
 
 int dctae_spectrum_tokens(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const int64_t* tok_off,
@@ -929,8 +829,9 @@ int dctae_spectrum_tokens(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_i
   if (!ctx) return DCTAE_EINVAL;
   if (!tok_off || !scores_dev) return fail(ctx, DCTAE_EINVAL, "tok_off and scores_dev are required");
   hipSetDevice(ctx->device);
-  return encode_impl(ctx, cfg, imgs, nullptr, nullptr, nullptr, nullptr, tok_off, tokens_dev, scores_dev,
-                     (hipStream_t)stream);
+  EncCall c{};
+  c.cfg = cfg, c.imgs = imgs, c.tok_off_user = tok_off, c.tokens_dev = tokens_dev, c.scores_dev = scores_dev;
+  return encode_call(ctx, c, (hipStream_t)stream);
 }
 
 // Full-image orthonormal 2-D DCT (util.py:333-338 on the whole (3, H, W) image)

@@ -180,6 +180,32 @@ void xcd_deal_tiles(std::vector<TileRef>& t, const GemmProblem* probs, int share
   t.swap(out);
 }
 
+// XCD-aware order of the column blocks (image, channel, tile column, count) of a
+// compile-time plan kernel (speed only; any order is correct): blocks b and
+// b+8 are dealt to the same XCD, so give all the blocks of one (image, channel)
+// the same b % 8 and consecutive b / 8 — the 56-byte row slices of
+// neighbouring tile columns then share that XCD's L2 lines.
+void xcd_deal_col_blocks(std::vector<int4>& L) {
+  if (L.size() < 16) return;
+  // units = runs of blocks with the same (image, channel), in list order
+  std::vector<std::vector<int4>> lanes(8);
+  size_t u = 0;
+  for (size_t a0 = 0; a0 < L.size(); ++u) {
+    size_t a1 = a0 + 1;
+    while (a1 < L.size() && L[a1].x == L[a0].x && L[a1].y == L[a0].y) ++a1;
+    lanes[u % 8].insert(lanes[u % 8].end(), L.begin() + a0, L.begin() + a1);
+    a0 = a1;
+  }
+  std::vector<int4> out;
+  out.reserve(L.size());
+  size_t maxlen = 0;
+  for (auto& l : lanes) maxlen = std::max(maxlen, l.size());
+  for (size_t q = 0; q < maxlen; ++q)
+    for (int x = 0; x < 8; ++x)
+      if (q < lanes[x].size()) out.push_back(lanes[x][q]);
+  L.swap(out);
+}
+
 void add_tiles(std::vector<TileRef>& t, int prob, const GemmProblem& g) {
   int tm = (g.M + g.tile_m - 1) / g.tile_m;
   for (int i = 0; i < tm * g.tiles_n; ++i) t.push_back({prob, i});
