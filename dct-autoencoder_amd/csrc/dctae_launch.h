@@ -41,6 +41,8 @@ void launch_rows_fused(const GemmProblem* probs, const TileRef* tiles, int n_til
 // share 2 (the encode's column GEMM: B = T, sBn = 1): dma_cols = k_gemm_h2c
 void launch_gemm_h2(const GemmProblem* probs, const TileRef* tiles, int n_tiles, hipStream_t s, int share, bool dma,
                     bool dma_cols);
+// dctae_gemm_dma.hip: the two LDS-DMA forms, k_gemm_h2r (share 1) and k_gemm_h2c (share 2); launch_gemm_h2 dispatches
+void launch_gemm_h2_dma(const GemmProblem* probs, const TileRef* tiles, int n_tiles, hipStream_t s, int share);
 void split_matrix_h2(const float* m, int R, int K, std::vector<uint16_t>& out, int* Rp, int* Kp, int* e_out);
 void launch_tile_epilogue(const ImgDesc* imgs, int n_img, int max_T, const float* ws, const EncParams& ep,
                           const TokenSinks& sk, hipStream_t s, const int2* list = nullptr, int n_list = 0);

@@ -21,6 +21,7 @@
 // torch's: results are not bit-equal to nn.Linear, see tests/test_gpu_lfq_proj.py).
 #include "dctae_device.h"
 #include "dctae_launch.h"
+#include "dctae_mfma_tile.h"
 
 #include <cmath>
 
@@ -381,12 +382,7 @@ __global__ __launch_bounds__(1024) void k_split_w_h2(const float* __restrict__ w
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int i = 1; i < 16; ++i) m = max(m, part[i]);
-    int e = 0;
-    if (m != 0u && m < 0x7f800000u) {
-      frexpf(__uint_as_float(m), &e);
-      e = 14 - e;
-    }
-    ex = e;
+    ex = h2_matrix_exp(m);
   }
   __syncthreads();
   const float sc = ldexpf(1.0f, ex);
