@@ -49,6 +49,12 @@ class Images(C.Structure):
                 ("n_img", C.c_int32)]
 
 
+class ImagesU8(C.Structure):
+    """dctae_images_u8 (include/dctae_u8.h): uint8 pixels, img_off in bytes"""
+    _fields_ = [("rgb_dev", C.c_void_p), ("img_off", C.POINTER(C.c_int64)), ("hw", C.POINTER(C.c_int32)),
+                ("n_img", C.c_int32)]
+
+
 class Packing(C.Structure):
     _fields_ = [("row", C.POINTER(C.c_int32)), ("col", C.POINTER(C.c_int32)), ("k", C.POINTER(C.c_int32)),
                 ("local_id", C.POINTER(C.c_int32)), ("row_len", C.POINTER(C.c_int32)), ("n_rows", C.c_int32)]
@@ -96,6 +102,14 @@ _SIGS = {
                                C.POINTER(LFQCfg), _P, _P, C.POINTER(PackedOut), _P], C.c_int),
     "dctae_spectrum_tokens": ([_P, C.POINTER(FECfg), C.POINTER(Images), C.POINTER(C.c_int64), _P, _P, _P],
                               C.c_int),
+    # include/dctae_u8.h: the byte-image entries
+    "dctae_encode_u8": ([_P, C.POINTER(FECfg), C.POINTER(ImagesU8), C.POINTER(Packing), C.POINTER(Norm),
+                         C.POINTER(LFQCfg), C.POINTER(PackedOut), _P], C.c_int),
+    "dctae_encode_lfq_proj_u8": ([_P, C.POINTER(FECfg), C.POINTER(ImagesU8), C.POINTER(Packing), C.POINTER(Norm),
+                                  C.POINTER(LFQCfg), _P, _P, C.POINTER(PackedOut), _P], C.c_int),
+    "dctae_spectrum_tokens_u8": ([_P, C.POINTER(FECfg), C.POINTER(ImagesU8), C.POINTER(C.c_int64), _P, _P, _P],
+                                 C.c_int),
+    "dctae_u8_to_f32": ([_P, _P, C.c_int64, _P, _P], C.c_int),
     "dctae_dct2": ([_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P], C.c_int),
     "dctae_patch_spectrum": ([_P, C.POINTER(FECfg), _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P],
                              C.c_int),

@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import FECfg, Images, LFQCfg, Norm, PackedOut, Packing, VQCfg, i32, i64, ptr
+from ._lib import FECfg, Images, ImagesU8, LFQCfg, Norm, PackedOut, Packing, VQCfg, i32, i64, ptr
 
 
 @dataclass(frozen=True)
@@ -122,10 +122,67 @@ def batch_image_set(x: torch.Tensor) -> Tuple[Images, torch.device, list]:
     return desc, dev, [x, offs, hw]
 
 
+def _u8_image(im: torch.Tensor) -> torch.Tensor:
+    """a uint8 tensor as the kernels read it: itself when contiguous, else a contiguous copy (as
+    image_set does for fp32 images: the kernels take dense (3, H, W) planes only)"""
+    if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8:
+        raise TypeError(f"uint8 images expected, got {getattr(im, 'dtype', type(im))}")
+    return im if im.is_contiguous() else im.contiguous()
+
+
+def image_set_u8(images: Sequence[torch.Tensor]) -> Tuple[ImagesU8, torch.device, list]:
+    """image_set for (3,H,W) uint8 device images: byte offsets and no copies
+    of contiguous images, with one exception: a 512-wide image at a base not
+    4-byte aligned is cloned (the 512-wide row kernel loads four pixels at
+    once: include/dctae_u8.h).  A non-contiguous image is copied dense."""
+    imgs = [_u8_image(im) for im in images]
+    dev = _check_dev(*imgs)
+    for im in imgs:
+        if im.dim() != 3:
+            raise AssertionError(f"expected a (c, h, w) image, got {tuple(im.shape)}")
+    imgs = [im.clone() if (im.shape[2] == 512 and im.data_ptr() % 4) else im for im in imgs]
+    ptrs = [im.data_ptr() for im in imgs]
+    base = min(ptrs) if ptrs else 0
+    offs = [p - base for p in ptrs]
+    hw = []
+    for im in imgs:
+        hw += [im.shape[1], im.shape[2]]
+    offs, hw = i64(offs), i32(hw)
+    desc = ImagesU8(C.c_void_p(base), C.cast(offs, C.POINTER(C.c_int64)), C.cast(hw, C.POINTER(C.c_int32)), len(imgs))
+    return desc, dev, [imgs, offs, hw]
+
+
+def batch_image_set_u8(x: torch.Tensor) -> Tuple[ImagesU8, torch.device, list]:
+    """(B,3,H,W) uint8 contiguous device tensor (a 512-wide batch at a base not
+    4-byte aligned is cloned: 3 * H * 512 keeps every image of it aligned)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise AssertionError("expected (B, c, h, w)")
+    x = _u8_image(x)
+    dev = _check_dev(x)
+    B, c, H, W = x.shape
+    if W == 512 and x.data_ptr() % 4:
+        x = x.clone()
+    per = c * H * W
+    offs, hw = i64([i * per for i in range(B)]), i32([H, W] * B)
+    desc = ImagesU8(C.c_void_p(x.data_ptr()), C.cast(offs, C.POINTER(C.c_int64)), C.cast(hw, C.POINTER(C.c_int32)), B)
+    return desc, dev, [x, offs, hw]
+
+
+def u8_to_f32(x: torch.Tensor) -> torch.Tensor:
+    """dctae_u8_to_f32: the fp32 tensor x / 255 of a uint8 device tensor (the
+    values the byte-image encode means)."""
+    x = _u8_image(x)
+    dev = _check_dev(x)
+    ctx = _lib.context(dev)
+    y = torch.empty(x.shape, dtype=torch.float32, device=dev)
+    ctx.check(ctx.lib.dctae_u8_to_f32(ctx.h, ptr(x), x.numel(), ptr(y), _lib.stream_ptr(dev)), "dctae_u8_to_f32")
+    return y
+
+
 def encode(imgs_desc: Images, dev: torch.device, p: FEParams, plan, n_rows: int, seq_len: int,
            norm: Optional[NormState], lfq: Optional[LFQCfg], want_codes=True, want_patches=False,
            want_raw=False, want_scores=False, out=None):
-    """dctae_encode: returns dict of packed device tensors."""
+    """dctae_encode (dctae_encode_u8 for an ImagesU8 descriptor): returns dict of packed device tensors."""
     ctx = _lib.context(dev)
     S = seq_len
     PP = p.patch_size ** 2
@@ -155,10 +212,11 @@ def encode(imgs_desc: Images, dev: torch.device, p: FEParams, plan, n_rows: int,
     po = PackedOut(ptr(res.get("codes")), ptr(res["positions"]), ptr(res["channels"]), ptr(res["image_ids"]),
                    ptr(res["key_pad_mask"]), ptr(res.get("patches")), ptr(res.get("raw")), ptr(res.get("scores")))
     nc = norm.c() if norm is not None else None
-    rc = ctx.lib.dctae_encode(ctx.h, C.byref(p.c(S)), C.byref(imgs_desc), C.byref(pk),
-                              C.byref(nc) if nc is not None else None,
-                              C.byref(lfq) if lfq is not None else None, C.byref(po), _lib.stream_ptr(dev))
-    ctx.check(rc, "dctae_encode")
+    name = "dctae_encode_u8" if isinstance(imgs_desc, ImagesU8) else "dctae_encode"
+    rc = getattr(ctx.lib, name)(ctx.h, C.byref(p.c(S)), C.byref(imgs_desc), C.byref(pk),
+                                C.byref(nc) if nc is not None else None,
+                                C.byref(lfq) if lfq is not None else None, C.byref(po), _lib.stream_ptr(dev))
+    ctx.check(rc, name)
     return res
 
 

@@ -2,6 +2,7 @@
 // See include/dctae.h for the contract of every entry point; dctae_ctx.h
 // lists the host units.
 #include "dctae_ctx.h"
+#include "../../include/dctae_u8.h"
 
 using namespace dctae;
 
@@ -298,6 +299,16 @@ int dctae_synth_images(dctae_ctx* ctx, uint64_t seed, int64_t first_index, int32
   if (n_img == 0) return 0;
   Timer t(ctx, (hipStream_t)stream, "synth");
   launch_synth(seed, first_index, n_img, H, W, rgb_dev, (hipStream_t)stream);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_u8_to_f32(dctae_ctx* ctx, const uint8_t* x_dev, int64_t n, float* y_dev, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (n < 0 || (n > 0 && (!x_dev || !y_dev))) return fail(ctx, DCTAE_EINVAL, "bad u8_to_f32 args");
+  if (n == 0) return 0;
+  hipSetDevice(ctx->device);
+  launch_u8_to_f32(x_dev, n, y_dev, (hipStream_t)stream);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }

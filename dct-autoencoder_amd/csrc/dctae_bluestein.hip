@@ -222,9 +222,9 @@ constexpr int kBsItems = 1;
 
 // rows: block = kBsItems groups of 2G rows of one image from y0; per group the
 // jobs (row pair g, channel c)
-template <int L>
+template <int L, typename Px>
 __global__ __launch_bounds__(Bs<L>::NT) void k_bs_rows(const ImgDesc* __restrict__ imgs, const FftPlan* __restrict__ plans,
-                                                 const int2* __restrict__ blocks, const float* __restrict__ rgb,
+                                                 const int2* __restrict__ blocks, const Px* __restrict__ rgb,
                                                  float* __restrict__ ws, const float2* __restrict__ tabs, ColorMats cm,
                                                  int ablate) {
   using S = Bs<L>;
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(Bs<L>::NT) void k_bs_rows(const ImgDesc* __restrict
   const BsTabs t = bs_tabs(plans[d.plan_w], tabs);
   const int N = d.W, Kw = d.Kw, H = d.H, tid0 = threadIdx.x;
   const int64_t hw = (int64_t)H * N;
-  const float* src = rgb + d.rgb_off;
+  const Px* src = rgb + d.rgb_off;
   float* lf = reinterpret_cast<float*>(lds);
   const float gam = 0.430000007152557373046875f;
   const int job = tid0 / S::TPJ;
@@ -252,9 +252,10 @@ __global__ __launch_bounds__(Bs<L>::NT) void k_bs_rows(const ImgDesc* __restrict
         const int px = tid + S::NT * i, y = yb + r;
         const bool ok = px < N && y < H;
         const int64_t o = ok ? (int64_t)y * N + px : 0;
-        rgbv[r * PXI + i][0] = ok ? src[o] : 0.f;
-        rgbv[r * PXI + i][1] = ok ? src[hw + o] : 0.f;
-        rgbv[r * PXI + i][2] = ok ? src[2 * hw + o] : 0.f;
+        // as loaded (px_value at the use; 0 is the value 0 for either pixel type)
+        rgbv[r * PXI + i][0] = ok ? load_px_raw(&src[o]) : 0.f;
+        rgbv[r * PXI + i][1] = ok ? load_px_raw(&src[hw + o]) : 0.f;
+        rgbv[r * PXI + i][2] = ok ? load_px_raw(&src[2 * hw + o]) : 0.f;
       }
   };
   load_rgb(jb.y, tid0);
@@ -273,7 +274,8 @@ __global__ __launch_bounds__(Bs<L>::NT) void k_bs_rows(const ImgDesc* __restrict
         for (int i = 0; i < PXI; ++i) {
           const int px = tid + S::NT * i;
           if (px >= N) continue;
-          const float R_ = rgbv[r * PXI + i][0], G_ = rgbv[r * PXI + i][1], B_ = rgbv[r * PXI + i][2];
+          const float R_ = px_value<Px>(rgbv[r * PXI + i][0]), G_ = px_value<Px>(rgbv[r * PXI + i][1]),
+                      B_ = px_value<Px>(rgbv[r * PXI + i][2]);
           const float l0 = signed_pow_fast(mat3_row(cm.rgb2lms, 0, R_, G_, B_), gam);
           const float l1 = signed_pow_fast(mat3_row(cm.rgb2lms, 1, R_, G_, B_), gam);
           const float l2 = signed_pow_fast(mat3_row(cm.rgb2lms, 2, R_, G_, B_), gam);
@@ -393,16 +395,26 @@ __global__ __launch_bounds__(Bs<L>::NT) void k_bs_cols(const ImgDesc* __restrict
 int bs_rows_per_block(int L) { return kBsItems * 2 * (2048 / L); }
 int bs_cols_per_block(int L) { return kBsItems * 2 * 3 * (2048 / L); }
 
-void launch_bs_rows(int L, const ImgDesc* imgs, const FftPlan* plans, const int2* blocks, int n_blocks,
-                    const float* rgb, float* ws, const float2* tabs, const ColorMats& cm, hipStream_t s, int ablate) {
-  if (n_blocks <= 0) return;
+template <typename Px>
+static void bs_rows(int L, const ImgDesc* imgs, const FftPlan* plans, const int2* blocks, int n_blocks, const Px* rgb,
+                    float* ws, const float2* tabs, const ColorMats& cm, hipStream_t s, int ablate) {
   switch (L) {
-    case 256: hipLaunchKernelGGL(k_bs_rows<256>, dim3(n_blocks), dim3(Bs<256>::NT), 0, s, imgs, plans, blocks, rgb, ws, tabs, cm, ablate); break;
-    case 512: hipLaunchKernelGGL(k_bs_rows<512>, dim3(n_blocks), dim3(Bs<512>::NT), 0, s, imgs, plans, blocks, rgb, ws, tabs, cm, ablate); break;
-    case 1024: hipLaunchKernelGGL(k_bs_rows<1024>, dim3(n_blocks), dim3(Bs<1024>::NT), 0, s, imgs, plans, blocks, rgb, ws, tabs, cm, ablate); break;
-    case 2048: hipLaunchKernelGGL(k_bs_rows<2048>, dim3(n_blocks), dim3(Bs<2048>::NT), 0, s, imgs, plans, blocks, rgb, ws, tabs, cm, ablate); break;
+    case 256: hipLaunchKernelGGL((k_bs_rows<256, Px>), dim3(n_blocks), dim3(Bs<256>::NT), 0, s, imgs, plans, blocks, rgb, ws, tabs, cm, ablate); break;
+    case 512: hipLaunchKernelGGL((k_bs_rows<512, Px>), dim3(n_blocks), dim3(Bs<512>::NT), 0, s, imgs, plans, blocks, rgb, ws, tabs, cm, ablate); break;
+    case 1024: hipLaunchKernelGGL((k_bs_rows<1024, Px>), dim3(n_blocks), dim3(Bs<1024>::NT), 0, s, imgs, plans, blocks, rgb, ws, tabs, cm, ablate); break;
+    case 2048: hipLaunchKernelGGL((k_bs_rows<2048, Px>), dim3(n_blocks), dim3(Bs<2048>::NT), 0, s, imgs, plans, blocks, rgb, ws, tabs, cm, ablate); break;
     default: break;
   }
+}
+
+void launch_bs_rows(int L, const ImgDesc* imgs, const FftPlan* plans, const int2* blocks, int n_blocks,
+                    const void* rgb, PixelType px, float* ws, const float2* tabs, const ColorMats& cm, hipStream_t s,
+                    int ablate) {
+  if (n_blocks <= 0) return;
+  if (px == PixelType::kU8)
+    bs_rows(L, imgs, plans, blocks, n_blocks, (const uint8_t*)rgb, ws, tabs, cm, s, ablate);
+  else
+    bs_rows(L, imgs, plans, blocks, n_blocks, (const float*)rgb, ws, tabs, cm, s, ablate);
 }
 
 void launch_bs_cols(int L, const ImgDesc* imgs, const FftPlan* plans, const int4* blocks, int n_blocks, float* ws,

@@ -2,6 +2,7 @@
 // dctae_spectrum_tokens, dctae_dct2 and dctae_patch_spectrum.
 #include "dctae_ctx.h"
 #include "dctae_enc_layout.h"
+#include "../../include/dctae_u8.h"
 
 using namespace dctae;
 
@@ -52,10 +53,29 @@ struct EncPlan {
   bool uniform = false;  // every image of the call has the same (H, W)
 };
 
+// The images of a call: dctae_images or dctae_images_u8, with the pixel type
+// as a tag (img_off counts pixels of that type).  ok = false: the caller's
+// descriptor pointer was NULL.
+struct ImageSet {
+  bool ok = false;
+  const void* rgb = nullptr;
+  const int64_t* img_off = nullptr;
+  const int32_t* hw = nullptr;
+  int32_t n_img = 0;
+  PixelType px = PixelType::kF32;
+  ImageSet() = default;
+  explicit ImageSet(const dctae_images* d) {
+    if (d) ok = true, rgb = d->rgb_dev, img_off = d->img_off, hw = d->hw, n_img = d->n_img;
+  }
+  explicit ImageSet(const dctae_images_u8* d) : px(PixelType::kU8) {
+    if (d) ok = true, rgb = d->rgb_dev, img_off = d->img_off, hw = d->hw, n_img = d->n_img;
+  }
+};
+
 // One encode call: its arguments and what they ask for.
 struct EncCall {
   const dctae_fe_cfg* cfg;
-  const dctae_images* imgs;
+  ImageSet imgs;
   const dctae_packing* pack;   // NULL: token mode
   const dctae_norm* norm;
   const dctae_lfq* lfq;
@@ -73,10 +93,10 @@ struct EncCall {
 int EncCall::check(dctae_ctx* ctx) {
   int rc = check_cfg(ctx, cfg);
   if (rc) return rc;
-  if (!imgs || imgs->n_img < 0 || (imgs->n_img > 0 && (!imgs->rgb_dev || !imgs->img_off || !imgs->hw)))
+  if (!imgs.ok || imgs.n_img < 0 || (imgs.n_img > 0 && (!imgs.rgb || !imgs.img_off || !imgs.hw)))
     return fail(ctx, DCTAE_EINVAL, "bad image descriptor");
   full = (pack != nullptr);
-  const int n = imgs->n_img;
+  const int n = imgs.n_img;
   const int P = cfg->patch_size, PP = P * P;
   want_codes = full && out && out->codes_dev;
   if (full) {
@@ -106,15 +126,19 @@ int EncCall::check(dctae_ctx* ctx) {
 // plan cache key: every input that shapes the launch sequence (the workspace
 // pointer is compared beside it: EncPlan::ws)
 std::vector<int64_t> EncCall::plan_key(const Options& opt) const {
-  const int n = imgs->n_img;
+  const int n = imgs.n_img;
   std::vector<int64_t> key;
   key.reserve(32 + 6ll * n + (full ? pack->n_rows : 0));
+  // byte images: the base's alignment is part of the key, since describe_images' refusal of a misaligned
+  // 512-wide image (dctae_u8.h) depends on rgb_dev + img_off and must not be skipped by a plan cached
+  // for the same offsets at another base
+  const int64_t px_key = imgs.px == PixelType::kU8 ? 1 + (int64_t)(((uintptr_t)imgs.rgb & 3) << 1) : 0;
   key.insert(key.end(), {(int64_t)full, n, cfg->patch_size, cfg->max_patch_h, cfg->max_patch_w, cfg->max_seq_len, ncb,
-                         (int64_t)want_raw, (int64_t)want_norm});
+                         (int64_t)want_raw, (int64_t)want_norm, px_key});
   push_plan_options(opt, key);
   for (int i = 0; i < n; ++i) {
-    key.push_back(imgs->img_off[i]);
-    key.push_back(((int64_t)imgs->hw[2 * i] << 32) | (uint32_t)imgs->hw[2 * i + 1]);
+    key.push_back(imgs.img_off[i]);
+    key.push_back(((int64_t)imgs.hw[2 * i] << 32) | (uint32_t)imgs.hw[2 * i + 1]);
     if (full) {
       key.push_back(((int64_t)pack->row[i] << 32) | (uint32_t)pack->col[i]);
       key.push_back(((int64_t)pack->k[i] << 32) | (uint32_t)pack->local_id[i]);
@@ -129,6 +153,11 @@ std::vector<int64_t> EncCall::plan_key(const Options& opt) const {
   return key;
 }
 
+// spec-1 (512-wide) rows run on k_rows512pk, else on k_fft_rows2<512, 16, 16>
+static bool rows512_kernel(const dctae_ctx* ctx, const dctae_fe_cfg* cfg) {
+  return ctx->opt.rows_kernel == 4 && cfg->max_patch_w == 32;
+}
+
 // the images of a call with their routes, and the FFT plans plan_w / plan_h index
 struct EncImages {
   std::vector<ImgDesc> D;
@@ -139,7 +168,7 @@ struct EncImages {
 static int describe_images(dctae_ctx* ctx, const EncCall& c, EncImages& im) {
   const dctae_fe_cfg* cfg = c.cfg;
   const dctae_packing* pack = c.pack;
-  const int n = c.imgs->n_img, P = cfg->patch_size, S = cfg->max_seq_len;
+  const int n = c.imgs.n_img, P = cfg->patch_size, S = cfg->max_seq_len;
   int rc;
   std::vector<ImgDesc>& D = im.D;
   std::vector<FftPlan>& plans = im.plans;
@@ -159,8 +188,8 @@ static int describe_images(dctae_ctx* ctx, const EncCall& c, EncImages& im) {
   };
   for (int i = 0; i < n; ++i) {
     ImgDesc& d = D[i];
-    if ((rc = describe(ctx, cfg, c.imgs->hw[2 * i], c.imgs->hw[2 * i + 1], d))) return rc;
-    d.rgb_off = c.imgs->img_off[i];
+    if ((rc = describe(ctx, cfg, c.imgs.hw[2 * i], c.imgs.hw[2 * i + 1], d))) return rc;
+    d.rgb_off = c.imgs.img_off[i];
     if (c.full) {
       d.row = pack->row[i];
       d.col = pack->col[i];
@@ -182,6 +211,11 @@ static int describe_images(dctae_ctx* ctx, const EncCall& c, EncImages& im) {
     // packed encodes of band images: item-major token staging (stage_pos; the
     // staging is internal there, while dctae_spectrum_tokens hands it out in flat order)
     if (c.full && d.tband) d.tband |= 2;
+    // k_rows512pk loads four byte pixels as one dword (dctae_u8.h: the alignment rule)
+    if (c.imgs.px == PixelType::kU8 && rows512_kernel(ctx, cfg) && row_route(d) == Route::kFft &&
+        plans[d.plan_w].spec == 1 && (((uintptr_t)c.imgs.rgb + (uint64_t)d.rgb_off) & 3))
+      return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": a 512-wide byte image on k_rows512pk must "
+                                     "start at a 4-byte aligned address (rgb_dev + img_off[i])");
   }
   if (c.full)
     for (int r = 0; r < pack->n_rows; ++r)
@@ -504,7 +538,7 @@ struct SideStream {
 struct EncLaunch {
   dctae_ctx* ctx;
   const dctae_fe_cfg* cfg;
-  const dctae_images* imgs;
+  const ImageSet& imgs;
   const EncPlan& E;
   hipStream_t s;             // the caller's stream
   uint8_t* pd;               // the uploaded plan
@@ -526,12 +560,12 @@ struct EncLaunch {
   // items [a, a + m) of the job's list on a stream, one spelling each.
   void rows_spec(const ChunkJob& j, int v, int a, int m, hipStream_t st) const {
     Timer t(ctx, st, "fft_rows");
-    launch_fft_rows_spec(v, j.desc.at(pd), j.fr[v].at(pd) + a, m, imgs->rgb_dev, E.ws,
+    launch_fft_rows_spec(v, j.desc.at(pd), j.fr[v].at(pd) + a, m, imgs.rgb, imgs.px, E.ws,
                          ctx->fft_tab + j.row_tab[v].tw_off, ctx->fft_tab + j.row_tab[v].post_off, ctx->cm, st);
   }
   void rows512(const ChunkJob& j, int a, int m, hipStream_t st) const {
     Timer t(ctx, st, "fft_rows");
-    launch_rows512(j.desc.at(pd), j.fr[1].at(pd) + a, m, imgs->rgb_dev, E.ws, ctx->fft_tab + j.row_tab[1].tw_off,
+    launch_rows512(j.desc.at(pd), j.fr[1].at(pd) + a, m, imgs.rgb, imgs.px, E.ws, ctx->fft_tab + j.row_tab[1].tw_off,
                    ctx->fft_tab + j.row_tab[1].post_off, ctx->cm, st);
   }
   void cols_band(const ChunkJob& j, int a, int m, hipStream_t st, bool allow_wide = true) const {
@@ -557,14 +591,14 @@ struct EncLaunch {
       int* flags = reinterpret_cast<int*>(amax + 2 * nj);
       for (int fixup = 0; fixup < 2; ++fixup) {
         Timer t(ctx, st, fixup ? "rows_fixup" : "rows_fused");
-        launch_rows_fused(j.gp.at(pd), j.fused_t.at(pd), j.fused_t.n, dd, imgs->rgb_dev, ctx->cm, amax, flags, nj, st,
-                          fixup != 0);
+        launch_rows_fused(j.gp.at(pd), j.fused_t.at(pd), j.fused_t.n, dd, imgs.rgb, imgs.px, ctx->cm, amax, flags, nj,
+                          st, fixup != 0);
       }
     }
     if (j.rows_t.n) {
       {
         Timer t(ctx, st, "rgb_to_ipt");
-        launch_rgb_to_ipt(dd, j.ipt.at(pd), j.ipt.n, imgs->rgb_dev, E.ws, ctx->cm, j.h2 ? amax : nullptr, st);
+        launch_rgb_to_ipt(dd, j.ipt.at(pd), j.ipt.n, imgs.rgb, imgs.px, E.ws, ctx->cm, j.h2 ? amax : nullptr, st);
       }
       Timer t(ctx, st, "gemm_rows");
       gemm(j, j.rows_t, st, 1);
@@ -572,17 +606,17 @@ struct EncLaunch {
     for (int l = 0; l < 4; ++l)
       if (j.br[l].n) {
         Timer t(ctx, st, "bs_rows");
-        launch_bs_rows(kBsL[l], dd, plans_d, j.br[l].at(pd), j.br[l].n, imgs->rgb_dev, E.ws, ctx->fft_tab, ctx->cm, st,
-                       ctx->opt.bs_ablate);
+        launch_bs_rows(kBsL[l], dd, plans_d, j.br[l].at(pd), j.br[l].n, imgs.rgb, imgs.px, E.ws, ctx->fft_tab, ctx->cm,
+                       st, ctx->opt.bs_ablate);
       }
     if (j.fr[0].n) {
       Timer t(ctx, st, "fft_rows");
-      launch_fft_rows(dd, plans_d, j.fr[0].at(pd), j.fr[0].n, j.lds_rows, imgs->rgb_dev, E.ws, ctx->fft_tab, ctx->cm,
-                      st);
+      launch_fft_rows(dd, plans_d, j.fr[0].at(pd), j.fr[0].n, j.lds_rows, imgs.rgb, imgs.px, E.ws, ctx->fft_tab,
+                      ctx->cm, st);
     }
     for (int v = 1; v < kVariants; ++v)
       if (j.fr[v].n) {
-        if (v == 1 && ctx->opt.rows_kernel == 4 && cfg->max_patch_w == 32)
+        if (v == 1 && rows512_kernel(ctx, cfg))
           rows512(j, 0, j.fr[v].n, st);
         else
           rows_spec(j, v, 0, j.fr[v].n, st);
@@ -799,10 +833,9 @@ static int encode_call(dctae_ctx* ctx, EncCall& c, hipStream_t s) {
   return 0;
 }
 
-extern "C" {
-
-int dctae_encode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const dctae_packing* pack,
-                 const dctae_norm* norm, const dctae_lfq* lfq, const dctae_packed_out* out, void* stream) {
+// the three encode entries for either image descriptor (the pixel type rides in the ImageSet)
+static int encode_packed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImageSet& imgs, const dctae_packing* pack,
+                         const dctae_norm* norm, const dctae_lfq* lfq, const dctae_packed_out* out, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
   if (!pack) return fail(ctx, DCTAE_EINVAL, "packing descriptor is NULL");
   hipSetDevice(ctx->device);
@@ -811,9 +844,9 @@ int dctae_encode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* im
   return encode_call(ctx, c, (hipStream_t)stream);
 }
 
-int dctae_encode_lfq_proj(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
-                          const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
-                          const float* w_in_dev, const float* b_in_dev, const dctae_packed_out* out, void* stream) {
+static int encode_packed_proj(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImageSet& imgs, const dctae_packing* pack,
+                              const dctae_norm* norm, const dctae_lfq* lfq, const float* w_in_dev,
+                              const float* b_in_dev, const dctae_packed_out* out, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
   if (!pack) return fail(ctx, DCTAE_EINVAL, "packing descriptor is NULL");
   if (!w_in_dev || !out || !out->codes_dev) return fail(ctx, DCTAE_EINVAL, "project_in weight and codes output required");
@@ -824,14 +857,49 @@ int dctae_encode_lfq_proj(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_i
   return encode_call(ctx, c, (hipStream_t)stream);
 }
 
-int dctae_spectrum_tokens(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const int64_t* tok_off,
-                          float* tokens_dev, float* scores_dev, void* stream) {
+static int encode_tokens(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImageSet& imgs, const int64_t* tok_off,
+                         float* tokens_dev, float* scores_dev, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
   if (!tok_off || !scores_dev) return fail(ctx, DCTAE_EINVAL, "tok_off and scores_dev are required");
   hipSetDevice(ctx->device);
   EncCall c{};
   c.cfg = cfg, c.imgs = imgs, c.tok_off_user = tok_off, c.tokens_dev = tokens_dev, c.scores_dev = scores_dev;
   return encode_call(ctx, c, (hipStream_t)stream);
+}
+
+extern "C" {
+
+int dctae_encode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const dctae_packing* pack,
+                 const dctae_norm* norm, const dctae_lfq* lfq, const dctae_packed_out* out, void* stream) {
+  return encode_packed(ctx, cfg, ImageSet(imgs), pack, norm, lfq, out, stream);
+}
+
+int dctae_encode_lfq_proj(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
+                          const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
+                          const float* w_in_dev, const float* b_in_dev, const dctae_packed_out* out, void* stream) {
+  return encode_packed_proj(ctx, cfg, ImageSet(imgs), pack, norm, lfq, w_in_dev, b_in_dev, out, stream);
+}
+
+int dctae_spectrum_tokens(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const int64_t* tok_off,
+                          float* tokens_dev, float* scores_dev, void* stream) {
+  return encode_tokens(ctx, cfg, ImageSet(imgs), tok_off, tokens_dev, scores_dev, stream);
+}
+
+// the byte-image entries (include/dctae_u8.h): the same calls, the pixel type apart
+int dctae_encode_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images_u8* imgs, const dctae_packing* pack,
+                    const dctae_norm* norm, const dctae_lfq* lfq, const dctae_packed_out* out, void* stream) {
+  return encode_packed(ctx, cfg, ImageSet(imgs), pack, norm, lfq, out, stream);
+}
+
+int dctae_encode_lfq_proj_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images_u8* imgs,
+                             const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
+                             const float* w_in_dev, const float* b_in_dev, const dctae_packed_out* out, void* stream) {
+  return encode_packed_proj(ctx, cfg, ImageSet(imgs), pack, norm, lfq, w_in_dev, b_in_dev, out, stream);
+}
+
+int dctae_spectrum_tokens_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images_u8* imgs,
+                             const int64_t* tok_off, float* tokens_dev, float* scores_dev, void* stream) {
+  return encode_tokens(ctx, cfg, ImageSet(imgs), tok_off, tokens_dev, scores_dev, stream);
 }
 
 // Full-image orthonormal 2-D DCT (util.py:333-338 on the whole (3, H, W) image)

@@ -111,8 +111,9 @@ __device__ __forceinline__ float2 makhoul_w(const float* z, JobLayout L, int job
 // rows: RGB -> IPT -> row DCT (first Kw coefficients) -> T[c][y][kx]
 // one block = rows [y0, y0 + rows_per_block) of one image, 3 jobs per row
 // ---------------------------------------------------------------------------
+template <typename Px>
 __global__ __launch_bounds__(256) void k_fft_rows(const ImgDesc* __restrict__ imgs, const FftPlan* __restrict__ plans,
-                                                  const int2* __restrict__ blocks, const float* __restrict__ rgb,
+                                                  const int2* __restrict__ blocks, const Px* __restrict__ rgb,
                                                   float* __restrict__ ws, const float2* __restrict__ tabs,
                                                   ColorMats cm) {
   extern __shared__ float lds[];
@@ -127,13 +128,13 @@ __global__ __launch_bounds__(256) void k_fft_rows(const ImgDesc* __restrict__ im
   float* B = lds + rpb * 3 * js;
   const int tid = threadIdx.x, nth = blockDim.x;
   const int64_t hw = (int64_t)d.H * d.W;
-  const float* src = rgb + d.rgb_off + (int64_t)y0 * N;
+  const Px* src = rgb + d.rgb_off + (int64_t)y0 * N;
   const float gam = 0.430000007152557373046875f;
   const bool odd = plp->odd != 0;   // block-uniform
   for (int e = tid; e < rows * N; e += nth) {
     const int r = e / N, px = e - r * N;
     const int64_t o = (int64_t)r * N + px;
-    const float R_ = src[o], G_ = src[hw + o], B_ = src[2 * hw + o];
+    const float R_ = load_px(&src[o]), G_ = load_px(&src[hw + o]), B_ = load_px(&src[2 * hw + o]);
     const float l0 = signed_pow_fast(mat3_row(cm.rgb2lms, 0, R_, G_, B_), gam);
     const float l1 = signed_pow_fast(mat3_row(cm.rgb2lms, 1, R_, G_, B_), gam);
     const float l2 = signed_pow_fast(mat3_row(cm.rgb2lms, 2, R_, G_, B_), gam);
@@ -281,8 +282,10 @@ size_t fft_kernel_setup(int device) {
   if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || v <= 0)
     v = 64 * 1024;
   size_t lim = (size_t)v;
-  if (hipFuncSetAttribute((const void*)k_fft_rows, hipFuncAttributeMaxDynamicSharedMemorySize, v) != hipSuccess ||
-      hipFuncSetAttribute((const void*)k_fft_cols, hipFuncAttributeMaxDynamicSharedMemorySize, v) != hipSuccess) {
+  const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
+  if (hipFuncSetAttribute((const void*)k_fft_rows<float>, attr, v) != hipSuccess ||
+      hipFuncSetAttribute((const void*)k_fft_rows<uint8_t>, attr, v) != hipSuccess ||
+      hipFuncSetAttribute((const void*)k_fft_cols, attr, v) != hipSuccess) {
     lim = 64 * 1024;
   }
   (void)hipGetLastError();  // never leave a sticky error for the caller's runtime
@@ -290,9 +293,15 @@ size_t fft_kernel_setup(int device) {
 }
 
 void launch_fft_rows(const ImgDesc* imgs, const FftPlan* plans, const int2* blocks, int n_blocks, size_t lds,
-                     const float* rgb, float* ws, const float2* tabs, const ColorMats& cm, hipStream_t s) {
+                     const void* rgb, PixelType px, float* ws, const float2* tabs, const ColorMats& cm,
+                     hipStream_t s) {
   if (n_blocks <= 0) return;
-  hipLaunchKernelGGL(k_fft_rows, dim3(n_blocks), dim3(256), lds, s, imgs, plans, blocks, rgb, ws, tabs, cm);
+  if (px == PixelType::kU8)
+    hipLaunchKernelGGL(k_fft_rows<uint8_t>, dim3(n_blocks), dim3(256), lds, s, imgs, plans, blocks,
+                       (const uint8_t*)rgb, ws, tabs, cm);
+  else
+    hipLaunchKernelGGL(k_fft_rows<float>, dim3(n_blocks), dim3(256), lds, s, imgs, plans, blocks, (const float*)rgb,
+                       ws, tabs, cm);
 }
 
 void launch_fft_cols(const ImgDesc* imgs, const FftPlan* plans, const int4* blocks, int n_blocks, size_t lds,

@@ -27,8 +27,8 @@ struct RowsLds {
   float2 z[4][3][MP];
 };
 
-template <int N, int R1, int R2>
-__device__ __forceinline__ void rows2_item(const ImgDesc& d, int y_first, const float* __restrict__ rgb,
+template <int N, int R1, int R2, typename Px>
+__device__ __forceinline__ void rows2_item(const ImgDesc& d, int y_first, const Px* __restrict__ rgb,
                                            float* __restrict__ T, RowsLds<N>& L, const float2* post_s,
                                            const float2* tw_s, const ColorMats& cm) {
   constexpr int M = N / 2;
@@ -48,7 +48,7 @@ __device__ __forceinline__ void rows2_item(const ImgDesc& d, int y_first, const 
   float* zf2 = reinterpret_cast<float*>(z[2]);
   const int H = d.H, Kw = d.Kw;
   const int64_t hw = (int64_t)H * N;
-  const float* src = rgb + d.rgb_off;
+  const Px* src = rgb + d.rgb_off;
   const float gam = 0.430000007152557373046875f;
   // ---- lane-invariant index maps (the same for every row)
   int zo[PX];                               // Makhoul slot of pixel lane + 64 i
@@ -77,9 +77,9 @@ __device__ __forceinline__ void rows2_item(const ImgDesc& d, int y_first, const 
       const int px = lane + 64 * i;
       if (px < N && y < H) {
         const int64_t o = (int64_t)y * N + px;
-        pr[i] = src[o];
-        pg[i] = src[hw + o];
-        pb[i] = src[2 * hw + o];
+        pr[i] = load_px(&src[o]);
+        pg[i] = load_px(&src[hw + o]);
+        pb[i] = load_px(&src[2 * hw + o]);
       }
     }
   };
@@ -150,9 +150,9 @@ __device__ __forceinline__ void rows2_item(const ImgDesc& d, int y_first, const 
   }
 }
 
-template <int N, int R1, int R2>
+template <int N, int R1, int R2, typename Px>
 __global__ __launch_bounds__(256) void k_fft_rows2(const ImgDesc* __restrict__ imgs, const int2* __restrict__ blocks,
-                                                   const float* __restrict__ rgb, float* __restrict__ ws,
+                                                   const Px* __restrict__ rgb, float* __restrict__ ws,
                                                    const float2* __restrict__ tw, const float2* __restrict__ post,
                                                    ColorMats cm) {
   constexpr int M = N / 2;
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void k_fft_rows2(const ImgDesc* __restrict__ i
   __syncthreads();
   const int2 jb = blocks[blockIdx.x];
   const ImgDesc d = imgs[jb.x];
-  rows2_item<N, R1, R2>(d, jb.y, rgb, ws + d.ws_t, L, post_s, tw_s, cm);
+  rows2_item<N, R1, R2, Px>(d, jb.y, rgb, ws + d.ws_t, L, post_s, tw_s, cm);
 }
 
 // ---------------------------------------------------------------------------
@@ -183,9 +183,9 @@ struct Rows224pLds {
   float2 z[4][3 * RW][MP];
 };
 
-template <int RW>
+template <int RW, typename Px>
 __global__ __launch_bounds__(256) void k_rows224p(const ImgDesc* __restrict__ imgs, const int2* __restrict__ blocks,
-                                                  const float* __restrict__ rgb, float* __restrict__ ws,
+                                                  const Px* __restrict__ rgb, float* __restrict__ ws,
                                                   const float2* __restrict__ tw, const float2* __restrict__ post,
                                                   ColorMats cm) {
   constexpr int N = 224, M = 112, R1 = 16, R2 = 7, B1 = 7, B2 = 16;
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void k_rows224p(const ImgDesc* __restrict__ im
   float2(*z)[MP] = L.z[wave];
   float* zf = reinterpret_cast<float*>(&z[0][0]);
   const int64_t hw = (int64_t)H * N;
-  const float* src = rgb + d.rgb_off + (int64_t)(live ? y0 : 0) * N;   // the wave's rows are contiguous
+  const Px* src = rgb + d.rgb_off + (int64_t)(live ? y0 : 0) * N;   // the wave's rows are contiguous
   const int nq = live ? min(RW, H - y0) * N : 0;
   float pr[PX + 1], pg[PX + 1], pb[PX + 1];
 #pragma unroll
@@ -217,9 +217,9 @@ __global__ __launch_bounds__(256) void k_rows224p(const ImgDesc* __restrict__ im
     // unconditional loads (pixels past the image's last row re-read pixel
     // lane; their results are never stored): no per-element control flow
     const int q = lane + 64 * i, qq = q < nq ? q : lane;
-    pr[i] = src[qq];
-    pg[i] = src[hw + qq];
-    pb[i] = src[2 * hw + qq];
+    pr[i] = load_px_raw(&src[qq]);   // as loaded; px_value at the use (below the barrier)
+    pg[i] = load_px_raw(&src[hw + qq]);
+    pb[i] = load_px_raw(&src[2 * hw + qq]);
   }
   {
     const float4* p4 = reinterpret_cast<const float4*>(post);
@@ -247,7 +247,9 @@ __global__ __launch_bounds__(256) void k_rows224p(const ImgDesc* __restrict__ im
   }
 #pragma unroll
   for (int i = 0; i < PX; i += 2) {
-    const cf r2 = (cf){pr[i], pr[i + 1]}, g2 = (cf){pg[i], pg[i + 1]}, b2 = (cf){pb[i], pb[i + 1]};
+    const cf r2 = (cf){px_value<Px>(pr[i]), px_value<Px>(pr[i + 1])},
+             g2 = (cf){px_value<Px>(pg[i]), px_value<Px>(pg[i + 1])},
+             b2 = (cf){px_value<Px>(pb[i]), px_value<Px>(pb[i + 1])};
     const cf l0 = splat_mix(cm.rgb2lms, 0, r2, g2, b2), l1 = splat_mix(cm.rgb2lms, 1, r2, g2, b2),
              l2 = splat_mix(cm.rgb2lms, 2, r2, g2, b2);
     const cf q0 = (cf){signed_pow_fast(l0.x, gam), signed_pow_fast(l0.y, gam)};
@@ -1198,13 +1200,25 @@ int fft_spec_id(int N, const int* radix, int npass, int P) {
 constexpr int kRows224pRW = 2;   // rows per wave of k_rows224p (2 or 3)
 int fft_spec_rows_per_block(int spec) { return spec == 2 ? 4 * kRows224pRW : (spec ? 16 : 0); }
 
-void launch_fft_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* rgb, float* ws,
+template <typename Px>
+static void fft_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const Px* rgb, float* ws,
                           const float2* tw, const float2* post, const ColorMats& cm, hipStream_t s) {
-  if (n_blocks <= 0) return;
   if (spec == 1)
-    hipLaunchKernelGGL((k_fft_rows2<512, 16, 16>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb, ws, tw, post, cm);
+    hipLaunchKernelGGL((k_fft_rows2<512, 16, 16, Px>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb, ws, tw, post,
+                       cm);
   else if (spec == 2)
-    hipLaunchKernelGGL((k_rows224p<kRows224pRW>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb, ws, tw, post, cm);
+    hipLaunchKernelGGL((k_rows224p<kRows224pRW, Px>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb, ws, tw, post,
+                       cm);
+}
+
+void launch_fft_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const void* rgb,
+                          PixelType px, float* ws, const float2* tw, const float2* post, const ColorMats& cm,
+                          hipStream_t s) {
+  if (n_blocks <= 0) return;
+  if (px == PixelType::kU8)
+    fft_rows_spec(spec, imgs, blocks, n_blocks, (const uint8_t*)rgb, ws, tw, post, cm, s);
+  else
+    fft_rows_spec(spec, imgs, blocks, n_blocks, (const float*)rgb, ws, tw, post, cm, s);
 }
 
 // spec 1 (N = 512): k_fft_cols7 over `list` (the job's 512-high images, one

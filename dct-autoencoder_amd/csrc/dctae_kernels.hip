@@ -80,8 +80,9 @@ __device__ __forceinline__ void block_amax(uint32_t m, uint32_t* dst) {
 // The RGB loads and folded IPT stores at the default cache policy
 // (nontemporal measured slower on config 4, round 5: rgb_to_ipt 1.41 -> 1.63
 // ms with NT loads, 1.93 ms with NT stores)
+template <typename Px>
 __global__ __launch_bounds__(256) void k_rgb_to_ipt(const ImgDesc* __restrict__ imgs, const int2* __restrict__ blocks,
-                                                    const float* __restrict__ rgb, float* __restrict__ ws,
+                                                    const Px* __restrict__ rgb, float* __restrict__ ws,
                                                     ColorMats cm, uint32_t* __restrict__ amax) {
   const int2 jb = blocks[blockIdx.x];
   const ImgDesc d = imgs[jb.x];
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void k_rgb_to_ipt(const ImgDesc* __restrict__ 
   const bool yfold = d.plan_h < 0;
   const int Hh = yfold ? (H + 1) / 2 : H;
   const int n_groups = Hh * Wh;   // < 2^31: the ABI's int32 image sides
-  const float* src = rgb + d.rgb_off;
+  const Px* src = rgb + d.rgb_off;
   float* dst = ws + d.ws_p;
   const float gam = 0.430000007152557373046875f;
   // pixel q of group k: 0 = (y, x), 1 = (y, x2), 2 = (y2, x), 3 = (y2, x2); absent
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(256) void k_rgb_to_ipt(const ImgDesc* __restrict__ 
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) px[k][q][c] = *(src + c * hw + o[q]);
+      for (int c = 0; c < 3; ++c) px[k][q][c] = load_px_raw(src + c * hw + o[q]);   // as loaded (px_value below)
   }
   uint32_t mx = 0;   // |max| of the values written (k_gemm_h2's operand scale)
 #pragma unroll
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(256) void k_rgb_to_ipt(const ImgDesc* __restrict__ 
     float p[4][3];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {   // util.py:70-82
-      const float r = px[k][q][0], g = px[k][q][1], b = px[k][q][2];
+      const float r = px_value<Px>(px[k][q][0]), g = px_value<Px>(px[k][q][1]), b = px_value<Px>(px[k][q][2]);
       const float l0 = signed_pow_fast(mat3_row(cm.rgb2lms, 0, r, g, b), gam);
       const float l1 = signed_pow_fast(mat3_row(cm.rgb2lms, 1, r, g, b), gam);
       const float l2 = signed_pow_fast(mat3_row(cm.rgb2lms, 2, r, g, b), gam);
@@ -201,9 +202,27 @@ void launch_fold_t(const ImgDesc* imgs, const int32_t* list, int n_list, int64_t
 
 int rgb_to_ipt_groups_per_block() { return kRgbGroups; }
 
-void launch_rgb_to_ipt(const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* rgb, float* ws,
+void launch_rgb_to_ipt(const ImgDesc* imgs, const int2* blocks, int n_blocks, const void* rgb, PixelType px, float* ws,
                        const ColorMats& cm, uint32_t* amax, hipStream_t s) {
-  if (n_blocks > 0) hipLaunchKernelGGL(k_rgb_to_ipt, dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb, ws, cm, amax);
+  if (n_blocks <= 0) return;
+  if (px == PixelType::kU8)
+    hipLaunchKernelGGL(k_rgb_to_ipt<uint8_t>, dim3(n_blocks), dim3(256), 0, s, imgs, blocks, (const uint8_t*)rgb, ws,
+                       cm, amax);
+  else
+    hipLaunchKernelGGL(k_rgb_to_ipt<float>, dim3(n_blocks), dim3(256), 0, s, imgs, blocks, (const float*)rgb, ws, cm,
+                       amax);
+}
+
+// the byte pixels' values as a plain kernel (dctae_u8_to_f32): one element per
+// thread and grid-stride step, byte loads at any alignment
+__global__ __launch_bounds__(256) void k_u8_to_f32(const uint8_t* __restrict__ x, int64_t n, float* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = load_px(x + i);
+}
+
+void launch_u8_to_f32(const uint8_t* x, int64_t n, float* y, hipStream_t s) {
+  if (n <= 0) return;
+  const int g = (int)std::min<int64_t>((n + 255) / 256, 1 << 16);
+  hipLaunchKernelGGL(k_u8_to_f32, dim3(g), dim3(256), 0, s, x, n, y);
 }
 
 // ipt (3,H,W) in place -> rgb written to out (3,H,W)

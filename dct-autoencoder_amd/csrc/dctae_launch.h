@@ -5,14 +5,18 @@
 #include <vector>
 
 #include "dctae_internal.h"
+#include "dctae_pixel.h"
 
 namespace dctae {
 
 void launch_synth(uint64_t seed, int64_t first, int32_t n_img, int32_t H, int32_t W, float* out, hipStream_t s);
 int rgb_to_ipt_groups_per_block();
 // amax (nullable): per job-local image, [2 i] receives the |max| bits of the folded IPT (k_gemm_h2)
-void launch_rgb_to_ipt(const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* rgb, float* ws,
+// rgb / px (here and in every row-pass launcher): the caller's pixels and their type, ImgDesc::rgb_off in pixels
+void launch_rgb_to_ipt(const ImgDesc* imgs, const int2* blocks, int n_blocks, const void* rgb, PixelType px, float* ws,
                        const ColorMats& cm, uint32_t* amax, hipStream_t s);
+// y[i] = x[i] / 255 (unit_from_byte), n elements
+void launch_u8_to_f32(const uint8_t* x, int64_t n, float* y, hipStream_t s);
 void launch_ipt_to_rgb(const ImgDesc* imgs, int n_img, int64_t max_hw, const float* ws, float* out,
                        const ColorMats& cm, hipStream_t s);
 void launch_color(const float* x, float* y, int64_t hw, int n_img, int dir, const ColorMats& cm, hipStream_t s);
@@ -35,8 +39,8 @@ void split_matrix_x3(const float* m, int R, int K, std::vector<uint16_t>& out, i
 int fused_pairs_per_block();
 int fused_max_n();
 void launch_rows_fused(const GemmProblem* probs, const TileRef* tiles, int n_tiles, const ImgDesc* imgs,
-                       const float* rgb, const ColorMats& cm, uint32_t* amax, int* flags, int n_img, hipStream_t s,
-                       bool fixup);
+                       const void* rgb, PixelType px, const ColorMats& cm, uint32_t* amax, int* flags, int n_img,
+                       hipStream_t s, bool fixup);
 // share 1 (the encode's row GEMM: A k-contiguous, sAm > 0): dma = k_gemm_h2r
 // share 2 (the encode's column GEMM: B = T, sBn = 1): dma_cols = k_gemm_h2c
 void launch_gemm_h2(const GemmProblem* probs, const TileRef* tiles, int n_tiles, hipStream_t s, int share, bool dma,
@@ -131,7 +135,8 @@ void launch_zero_pads(const float* x, const uint8_t* key_pad, int64_t n_tok, int
 
 size_t fft_kernel_setup(int device);
 void launch_fft_rows(const ImgDesc* imgs, const FftPlan* plans, const int2* blocks, int n_blocks, size_t lds,
-                     const float* rgb, float* ws, const float2* tabs, const ColorMats& cm, hipStream_t s);
+                     const void* rgb, PixelType px, float* ws, const float2* tabs, const ColorMats& cm,
+                     hipStream_t s);
 void launch_fft_cols(const ImgDesc* imgs, const FftPlan* plans, const int4* blocks, int n_blocks, size_t lds,
                      const float* ws, const float2* tabs, const EncParams& ep, const TokenSinks& sk, hipStream_t s);
 void launch_norm_thresholds(const float* med, const float* b, int64_t n, float eps, float lo, float hi, float* thr,
@@ -139,8 +144,9 @@ void launch_norm_thresholds(const float* med, const float* b, int64_t n, float e
 
 int fft_spec_id(int N, const int* radix, int npass, int P);
 int fft_spec_rows_per_block(int spec);
-void launch_fft_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* rgb, float* ws,
-                          const float2* tw, const float2* post, const ColorMats& cm, hipStream_t s);
+void launch_fft_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const void* rgb,
+                          PixelType px, float* ws, const float2* tw, const float2* post, const ColorMats& cm,
+                          hipStream_t s);
 void launch_fft_cols_spec(int spec, const ImgDesc* imgs, const int4* blocks, int n_blocks, const float* ws,
                           const float2* tw, const float2* post, const EncParams& ep, const TokenSinks& sk,
                           hipStream_t s, const int* list, int n_list, int qw);
@@ -156,7 +162,7 @@ void launch_idct_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, in
 
 void launch_idct_rows512(bool band, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, float* rgb,
                          const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s);
-void launch_rows512(const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* rgb, float* ws,
+void launch_rows512(const ImgDesc* imgs, const int2* blocks, int n_blocks, const void* rgb, PixelType px, float* ws,
                     const float2* tw, const float2* post, const ColorMats& cm, hipStream_t s);
 
 int cols7_grid(int n_list, int qw, int ipb);
@@ -169,7 +175,7 @@ void launch_cols512b(const ImgDesc* imgs, const int* list, int n_list, const flo
 int bs_rows_per_block(int L);
 int bs_cols_per_block(int L);
 void launch_bs_rows(int L, const ImgDesc* imgs, const FftPlan* plans, const int2* blocks, int n_blocks,
-                    const float* rgb, float* ws, const float2* tabs, const ColorMats& cm, hipStream_t s,
+                    const void* rgb, PixelType px, float* ws, const float2* tabs, const ColorMats& cm, hipStream_t s,
                     int ablate = 0);
 void launch_bs_cols(int L, const ImgDesc* imgs, const FftPlan* plans, const int4* blocks, int n_blocks, float* ws,
                     const float2* tabs, hipStream_t s, int ablate = 0);

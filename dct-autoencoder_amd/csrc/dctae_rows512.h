@@ -30,6 +30,7 @@
 #pragma once
 #include "dctae_device.h"
 #include "dctae_fft_common.h"
+#include "dctae_pixel.h"
 
 namespace dctae {
 
@@ -262,8 +263,12 @@ __device__ __forceinline__ void xpose4_rows(float (&r)[4]) {
 //    LDS and stored as whole 1 KB pieces (7 float4 stores per lane and
 //    channel, against 29 scattered 4-byte stores); k_cols512b's lane j of
 //    column kx then loads rows 64 b' + 4 j .. + 3 as one float4.
-template <bool band>
-__device__ __forceinline__ void rows512_item_pk(Rows512XchPk& X, const Rows512Tab& L, const float* __restrict__ img,
+// Px = float: lane j loads float4s; Px = uint8_t: one dword of four byte pixels
+// where the float4 was (the image base 4-byte aligned: dctae_u8.h), unpacked
+// by unit_from_dword (v_cvt_f32_ubyte0..3 and the exact / 255) outside this
+// body's contraction region (dctae_pixel.h); from there on the same code.
+template <bool band, typename Px>
+__device__ __forceinline__ void rows512_item_pk(Rows512XchPk& X, const Rows512Tab& L, const Px* __restrict__ img,
                                                 int H, int y0, float* T, uint32_t plane_bytes, const ColorMats& cm) {
 #pragma clang fp contract(fast)
   constexpr int N = 512, M = 256, KW = 448;
@@ -272,14 +277,30 @@ __device__ __forceinline__ void rows512_item_pk(Rows512XchPk& X, const Rows512Ta
   const int y = y0 + 4 * wv + g;
   const int yl = min(y, H - 1);
   const int64_t hw = (int64_t)H * N;
-  const float* src = img + (int64_t)yl * N + 4 * j;
+  const Px* src = img + (int64_t)yl * N + 4 * j;
 
   float4 I[3][8];
+  if constexpr (sizeof(Px) == 4) {
 #pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    I[0][b] = *reinterpret_cast<const float4*>(src + 64 * b);
-    I[1][b] = *reinterpret_cast<const float4*>(src + hw + 64 * b);
-    I[2][b] = *reinterpret_cast<const float4*>(src + 2 * hw + 64 * b);
+    for (int b = 0; b < 8; ++b) {
+      I[0][b] = *reinterpret_cast<const float4*>(src + 64 * b);
+      I[1][b] = *reinterpret_cast<const float4*>(src + hw + 64 * b);
+      I[2][b] = *reinterpret_cast<const float4*>(src + 2 * hw + 64 * b);
+    }
+  } else {
+    uint32_t U[3][8];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      U[0][b] = *reinterpret_cast<const uint32_t*>(src + 64 * b);
+      U[1][b] = *reinterpret_cast<const uint32_t*>(src + hw + 64 * b);
+      U[2][b] = *reinterpret_cast<const uint32_t*>(src + 2 * hw + 64 * b);
+    }
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        I[c][b] = make_float4(unit_from_dword(U[c][b], 0), unit_from_dword(U[c][b], 1), unit_from_dword(U[c][b], 2),
+                              unit_from_dword(U[c][b], 3));
   }
   // ---- IPT (util.py:70-82): A[c][b] = (ipt_c(x0), ipt_c(x2)), B[c][b] = (ipt_c(x3), ipt_c(x1))
   cf A[3][8], B[3][8];

@@ -6,8 +6,9 @@
 namespace dctae {
 
 // blocks[i] = (image, first row of a 16-row item)
+template <typename Px>
 __global__ __launch_bounds__(256) void k_rows512pk(const ImgDesc* __restrict__ imgs, const int2* __restrict__ blocks,
-                                                   const float* __restrict__ rgb, float* __restrict__ ws,
+                                                   const Px* __restrict__ rgb, float* __restrict__ ws,
                                                    const float2* __restrict__ tw, const float2* __restrict__ post,
                                                    ColorMats cm) {
   __shared__ Rows512XchPk x;
@@ -19,15 +20,20 @@ __global__ __launch_bounds__(256) void k_rows512pk(const ImgDesc* __restrict__ i
   // the two store layouts as separate bodies (one runtime branch inside the
   // channel loop costs ~80 VGPRs: 2 waves / SIMD instead of 3)
   if (d.tband)
-    rows512_item_pk<true>(x, t, rgb + d.rgb_off, d.H, jb.y, ws + d.ws_t, (uint32_t)(d.H * 448 * 4), cm);
+    rows512_item_pk<true, Px>(x, t, rgb + d.rgb_off, d.H, jb.y, ws + d.ws_t, (uint32_t)(d.H * 448 * 4), cm);
   else
-    rows512_item_pk<false>(x, t, rgb + d.rgb_off, d.H, jb.y, ws + d.ws_t, (uint32_t)(d.H * 448 * 4), cm);
+    rows512_item_pk<false, Px>(x, t, rgb + d.rgb_off, d.H, jb.y, ws + d.ws_t, (uint32_t)(d.H * 448 * 4), cm);
 }
 
-void launch_rows512(const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* rgb, float* ws,
+void launch_rows512(const ImgDesc* imgs, const int2* blocks, int n_blocks, const void* rgb, PixelType px, float* ws,
                     const float2* tw, const float2* post, const ColorMats& cm, hipStream_t s) {
   if (n_blocks <= 0) return;
-  hipLaunchKernelGGL(k_rows512pk, dim3(n_blocks), dim3(256), 0, s, imgs, blocks, rgb, ws, tw, post, cm);
+  if (px == PixelType::kU8)
+    hipLaunchKernelGGL(k_rows512pk<uint8_t>, dim3(n_blocks), dim3(256), 0, s, imgs, blocks, (const uint8_t*)rgb, ws,
+                       tw, post, cm);
+  else
+    hipLaunchKernelGGL(k_rows512pk<float>, dim3(n_blocks), dim3(256), 0, s, imgs, blocks, (const float*)rgb, ws, tw,
+                       post, cm);
 }
 
 }  // namespace dctae

@@ -62,9 +62,12 @@ constexpr int kFusedSE = 11;       // the first pass's operand scale 2^kFusedSE
 constexpr int kFusedPairs = 16;    // row pairs per block
 constexpr int kFusedTN = 256;      // output columns per parity
 
+// PxT: the caller's pixels, float or uint8_t (dctae_pixel.h): one buffer load
+// per pixel either way (a dword or a byte, the descriptor's range in bytes)
+template <typename PxT>
 __global__ __launch_bounds__(512, 1) void k_rows_fused(const GemmProblem* __restrict__ probs,
                                                       const TileRef* __restrict__ tiles, int n_tiles,
-                                                      const ImgDesc* __restrict__ imgs, const float* __restrict__ rgb,
+                                                      const ImgDesc* __restrict__ imgs, const PxT* __restrict__ rgb,
                                                       ColorMats cm, uint32_t* __restrict__ amax, int* __restrict__ flags,
                                                       int n_img, int fix) {
   constexpr int TN = kFusedTN, NPR = kFusedPairs;
@@ -145,7 +148,8 @@ __global__ __launch_bounds__(512, 1) void k_rows_fused(const GemmProblem* __rest
     const int yy = vy ? y : 0, y2 = H - 1 - yy;
     const bool yp = y2 != yy;
     const int hw = H * W;
-    const auto rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rgb + d.rgb_off), 0, 3 * hw * 4, 0x00020000);
+    const auto rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<PxT*>(rgb + d.rgb_off), 0,
+                                                         3 * hw * (int)sizeof(PxT), 0x00020000);
     typedef float Px[4][3];
     Px pxa, pxb;
     auto load_rgb = [&](Px& px, int k0) {
@@ -162,14 +166,18 @@ __global__ __launch_bounds__(512, 1) void k_rows_fused(const GemmProblem* __rest
       for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-          px[q][c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, (c * hw + o[q]) * 4, 0, 0));
+          // as loaded: the fp32 value, or the byte zero-extended (px_value in pix(), after the wait)
+          if constexpr (sizeof(PxT) == 4)
+            px[q][c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrsrc, (c * hw + o[q]) * 4, 0, 0));
+          else
+            px[q][c] = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rrsrc, c * hw + o[q], 0, 0));
     };
     bool bad = false;
     uint32_t fmx = 0;   // |max| of the folded values (the fix-up's scale)
     float pi[4][3];     // the IPT of the chunk position's 4 pixels
     // the colour transform of pixel q (util.py:70-82, k_rgb_to_ipt's arithmetic)
     auto pix = [&](const Px& px, int q) {
-      const float r = px[q][0], g = px[q][1], b = px[q][2];
+      const float r = px_value<PxT>(px[q][0]), g = px_value<PxT>(px[q][1]), b = px_value<PxT>(px[q][2]);
       const float l0 = signed_pow_fast(mat3_row(cm.rgb2lms, 0, r, g, b), gam);
       const float l1 = signed_pow_fast(mat3_row(cm.rgb2lms, 1, r, g, b), gam);
       const float l2 = signed_pow_fast(mat3_row(cm.rgb2lms, 2, r, g, b), gam);
@@ -373,14 +381,18 @@ int fused_pairs_per_block() { return kFusedPairs; }
 int fused_max_n() { return kFusedTN; }
 
 void launch_rows_fused(const GemmProblem* probs, const TileRef* tiles, int n_tiles, const ImgDesc* imgs,
-                       const float* rgb, const ColorMats& cm, uint32_t* amax, int* flags, int n_img, hipStream_t s,
-                       bool fixup) {
+                       const void* rgb, PixelType px, const ColorMats& cm, uint32_t* amax, int* flags, int n_img,
+                       hipStream_t s, bool fixup) {
   if (n_tiles <= 0) return;
   // the persistent first pass, or the fix-up's short grid-stride launch (every
   // block exits at once when no image is flagged)
   const int g = std::min((n_tiles + 7) & ~7, 256);
-  hipLaunchKernelGGL(k_rows_fused, dim3(g), dim3(512), 0, s, probs, tiles, n_tiles, imgs, rgb, cm, amax, flags, n_img,
-                     fixup ? 1 : 0);
+  if (px == PixelType::kU8)
+    hipLaunchKernelGGL(k_rows_fused<uint8_t>, dim3(g), dim3(512), 0, s, probs, tiles, n_tiles, imgs,
+                       (const uint8_t*)rgb, cm, amax, flags, n_img, fixup ? 1 : 0);
+  else
+    hipLaunchKernelGGL(k_rows_fused<float>, dim3(g), dim3(512), 0, s, probs, tiles, n_tiles, imgs, (const float*)rgb,
+                       cm, amax, flags, n_img, fixup ? 1 : 0);
 }
 
 }  // namespace dctae

@@ -398,7 +398,8 @@ class DCTAutoencoderFeatureExtractor:
     @torch.no_grad()
     def encode_batch(self, images, patchnorm=None, lfq=None, batch_size: Optional[int] = None,
                      return_patches: bool = False, return_raw: bool = False, return_scores: bool = False,
-                     ks: Optional[Sequence[int]] = None) -> List[Tuple[DCTPatches, Optional[torch.Tensor]]]:
+                     ks: Optional[Sequence[int]] = None,
+                     uint8_images: bool = False) -> List[Tuple[DCTPatches, Optional[torch.Tensor]]]:
         """preprocess every image, pack (iter_batches over ONE dataloader item
         holding all images, FE:179-287), PatchNorm (eval) and LFQ — the
         encode half of SURVEY §3.1-3.3 — in one launch sequence per batch.
@@ -408,20 +409,37 @@ class DCTAutoencoderFeatureExtractor:
         holds the PatchNorm output if return_patches, the raw DCT tokens if
         return_raw, else an empty (R, S, 0) tensor.  codes is None without lfq.
         With an overridden stage hook the reference's stages run one by one.
+
+        uint8_images=True: `images` holds uint8 RGB bytes (any other dtype
+        raises TypeError), each meaning the fp32 image ``u8.float() / 255``;
+        the row kernels read the bytes themselves and every output is
+        bit-identical to the call on that fp32 image (dctae_encode_u8).  The
+        stage hooks, where overridden, are handed those fp32 images.  The
+        bytes are read in place; only a non-contiguous image, or a 512-wide
+        one at an address that is not 4-byte aligned, is copied first.
         """
+        if uint8_images:
+            batched = isinstance(images, torch.Tensor) and images.dim() == 4
+            if not batched:
+                images = list(images)   # once: the check below must not use up an iterator
+            for im in ([images] if batched else images):
+                if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8:
+                    raise TypeError(f"uint8_images=True needs uint8 tensors, got {getattr(im, 'dtype', type(im))}")
         if self._staged_in() or self._overridden("_group_patches_by_max_seq_len") or \
                 self._overridden("_batch_groups"):
+            if uint8_images:   # the hooks see the fp32 images the bytes mean (dctae_u8_to_f32)
+                images = [_ops.u8_to_f32(self._dev(im)) for im in images]
             return self._encode_staged(images, patchnorm, lfq, batch_size, return_patches, return_raw)
         if isinstance(images, torch.Tensor) and images.dim() == 4:
             x = self._dev(images)
             B, _, H, W = x.shape
             sizes = [(H, W)] * B
-            desc, dev, keep = _ops.batch_image_set(x)
+            desc, dev, keep = (_ops.batch_image_set_u8 if uint8_images else _ops.batch_image_set)(x)
             img_list = None
         else:
             img_list = [self._dev(im) for im in images]
             sizes = [(im.shape[1], im.shape[2]) for im in img_list]
-            desc, dev, keep = _ops.image_set(img_list)
+            desc, dev, keep = (_ops.image_set_u8 if uint8_images else _ops.image_set)(img_list)
         if ks is None:
             ks = [self._k(h, w) for h, w in sizes]
         max_tok = self.max_patch_h * self.max_patch_w * self.channels
@@ -490,14 +508,15 @@ class DCTAutoencoderFeatureExtractor:
     @staticmethod
     def _subset(desc, keep, idx):
         import ctypes as C
-        from ._lib import Images, i32, i64
+        from ._lib import i32, i64
         offs = [keep[1][i] for i in idx]
         hw = []
         for i in idx:
             hw += [keep[2][2 * i], keep[2][2 * i + 1]]
         k2 = [i64(offs), i32(hw)]
         keep.append(k2)
-        return Images(desc.rgb_dev, C.cast(k2[0], C.POINTER(C.c_int64)), C.cast(k2[1], C.POINTER(C.c_int32)), len(idx))
+        return type(desc)(desc.rgb_dev, C.cast(k2[0], C.POINTER(C.c_int64)), C.cast(k2[1], C.POINTER(C.c_int32)),
+                          len(idx))   # Images or ImagesU8, as the call's descriptor
 
     @torch.no_grad()
     def decode_batch(self, dct_patches: DCTPatches, codes: torch.Tensor, patchnorm, lfq) -> List[torch.Tensor]:
@@ -529,10 +548,13 @@ class DCTAutoencoderFeatureExtractor:
 class BatchEncoder:
     """Pre-planned fused encode for a fixed batch geometry (the bench and
     serving path): packing plan, ctypes descriptors and output buffers are
-    built once; each call only enqueues the kernels (dctae_encode)."""
+    built once; each call only enqueues the kernels (dctae_encode).
+    input_dtype=torch.uint8: the calls take (B, 3, H, W) uint8 bytes meaning
+    ``u8.float() / 255`` (dctae_encode_u8 / dctae_encode_lfq_proj_u8), outputs
+    bit-identical to the fp32 encoder's on that tensor."""
 
     def __init__(self, fe: DCTAutoencoderFeatureExtractor, batch: int, height: int, width: int, patchnorm, lfq,
-                 device=None, want_patches: bool = False):
+                 device=None, want_patches: bool = False, input_dtype: torch.dtype = torch.float32):
         import ctypes as C
         from ._lib import Images, LFQCfg, Packing, PackedOut, i32, i64, ptr
         self.fe = fe
@@ -540,6 +562,10 @@ class BatchEncoder:
         if self.dev.index is None:   # "cuda" -> the current device, as tensors report it
             self.dev = torch.device(self.dev.type, torch.cuda.current_device())
         self.B, self.H, self.W = batch, height, width
+        if input_dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"BatchEncoder input_dtype: torch.float32 or torch.uint8, got {input_dtype}")
+        self.input_dtype = input_dtype
+        self._sfx = "_u8" if input_dtype == torch.uint8 else ""
         if fe.sample_patches_beta > 0:
             raise AssertionError("BatchEncoder needs sample_patches_beta == 0 (fixed k)")
         k = fe._tokens(height, width)
@@ -589,22 +615,27 @@ class BatchEncoder:
 
     def __call__(self, x: torch.Tensor):
         import ctypes as C
-        from ._lib import Images, ptr, stream_ptr
-        assert x.shape == (self.B, 3, self.H, self.W) and x.dtype == torch.float32 and x.is_contiguous()
+        from ._lib import Images, ImagesU8, ptr, stream_ptr
+        assert x.shape == (self.B, 3, self.H, self.W) and x.dtype == self.input_dtype and x.is_contiguous()
         assert x.device == self.dev
-        imgs = Images(C.c_void_p(x.data_ptr()), C.cast(self._keep[0], C.POINTER(C.c_int64)),
+        u8 = self.input_dtype == torch.uint8
+        if u8 and self.W == 512 and x.data_ptr() % 4:   # the 512-wide row kernel's dword loads (include/dctae_u8.h)
+            x = x.clone()
+        imgs = (ImagesU8 if u8 else Images)(C.c_void_p(x.data_ptr()), C.cast(self._keep[0], C.POINTER(C.c_int64)),
                       C.cast(self._keep[1], C.POINTER(C.c_int32)), self.B)
         if self.proj_staged:
             w, b = self.lfq._proj_w(self.lfq.project_in, self.dev)
-            rc = self.ctx.lib.dctae_encode_lfq_proj(self.ctx.h, C.byref(self._cfg), C.byref(imgs),
-                                                    C.byref(self.packing), C.byref(self._ncfg), C.byref(self.lcfg),
-                                                    ptr(w), ptr(b), C.byref(self.po), stream_ptr(self.dev))
-            self.ctx.check(rc, "dctae_encode_lfq_proj")
+            name = "dctae_encode_lfq_proj" + self._sfx
+            rc = getattr(self.ctx.lib, name)(self.ctx.h, C.byref(self._cfg), C.byref(imgs), C.byref(self.packing),
+                                             C.byref(self._ncfg), C.byref(self.lcfg), ptr(w), ptr(b),
+                                             C.byref(self.po), stream_ptr(self.dev))
+            self.ctx.check(rc, name)
             return self.out
-        rc = self.ctx.lib.dctae_encode(self.ctx.h, C.byref(self._cfg), C.byref(imgs), C.byref(self.packing),
-                                       C.byref(self._ncfg), None if self.proj else C.byref(self.lcfg),
-                                       C.byref(self.po), stream_ptr(self.dev))
-        self.ctx.check(rc, "dctae_encode")
+        name = "dctae_encode" + self._sfx
+        rc = getattr(self.ctx.lib, name)(self.ctx.h, C.byref(self._cfg), C.byref(imgs), C.byref(self.packing),
+                                         C.byref(self._ncfg), None if self.proj else C.byref(self.lcfg),
+                                         C.byref(self.po), stream_ptr(self.dev))
+        self.ctx.check(rc, name)
         if self.proj:
             w, b = self.lfq._proj_w(self.lfq.project_in, self.dev)
             from . import _ops
