@@ -142,6 +142,14 @@ _SIGS = {
     "dctae_decode_normed": ([_P, C.POINTER(FECfg), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                              C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P,
                              C.POINTER(Norm), _P, _P, _P], C.c_int),
+    # include/dctae_u8_out.h: the byte-output entries
+    "dctae_decode_u8": ([_P, C.POINTER(FECfg), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P,
+                         C.POINTER(Norm), C.POINTER(LFQCfg), _P, _P, _P, _P], C.c_int),
+    "dctae_decode_normed_u8": ([_P, C.POINTER(FECfg), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P,
+                                C.POINTER(Norm), _P, _P, _P], C.c_int),
+    "dctae_f32_to_u8": ([_P, _P, C.c_int64, _P, _P], C.c_int),
     "dctae_decode_backward": ([_P, C.POINTER(FECfg), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P,
                                _P, _P, _P, _P, _P, _P, _P], C.c_int),

@@ -179,6 +179,30 @@ def u8_to_f32(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def out_dtype_suffix(dtype: torch.dtype, what: str) -> str:
+    """the entry-point suffix of a decode output dtype: "" (fp32) or "_u8";
+    anything else is a TypeError naming ``what``"""
+    if dtype == torch.float32:
+        return ""
+    if dtype == torch.uint8:
+        return "_u8"
+    raise TypeError(f"{what}: torch.float32 or torch.uint8, got {dtype}")
+
+
+def f32_to_u8(x: torch.Tensor) -> torch.Tensor:
+    """dctae_f32_to_u8: the uint8 tensor of an fp32 device tensor by the byte
+    decode's rule, ``x.mul(255).add(0.5).clamp(0, 255).to(torch.uint8)`` as
+    torch computes it on the CPU (NaN gives 0): include/dctae_u8_out.h."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise TypeError(f"fp32 tensor expected, got {getattr(x, 'dtype', type(x))}")
+    x = x if x.is_contiguous() else x.contiguous()
+    dev = _check_dev(x)
+    ctx = _lib.context(dev)
+    y = torch.empty(x.shape, dtype=torch.uint8, device=dev)
+    ctx.check(ctx.lib.dctae_f32_to_u8(ctx.h, ptr(x), x.numel(), ptr(y), _lib.stream_ptr(dev)), "dctae_f32_to_u8")
+    return y
+
+
 def encode(imgs_desc: Images, dev: torch.device, p: FEParams, plan, n_rows: int, seq_len: int,
            norm: Optional[NormState], lfq: Optional[LFQCfg], want_codes=True, want_patches=False,
            want_raw=False, want_scores=False, out=None):
@@ -658,7 +682,8 @@ class DecodeTable:
         return self._c
 
     def images(self, flat: torch.Tensor) -> List[torch.Tensor]:
-        """the (3, H, W) views of a flat buffer in the decode's output layout"""
+        """the (3, H, W) views of a flat buffer in the decode's output layout
+        (fp32 or uint8: the offsets count elements of either)"""
         return [flat[o: o + self.channels * self.hw[2 * i] * self.hw[2 * i + 1]].view(
             self.channels, self.hw[2 * i], self.hw[2 * i + 1]) for i, o in enumerate(self.offs)]
 
@@ -668,18 +693,23 @@ def decode_table(p: FEParams, ids, key_pad, positions, channels, patch_sizes, or
 
 
 def _decode_call(ctx, cfg: FECfg, table: DecodeTable, ids, key_pad, pos, ch, norm: Optional[Norm],
-                 lfq: Optional[LFQCfg], codes, patches, out, normed: bool):
+                 lfq: Optional[LFQCfg], codes, patches, out, normed: bool, out_dtype: torch.dtype = torch.float32):
     """dctae_decode (from codes, or from patches when codes is None) or, normed,
     dctae_decode_normed of the packed batch into the flat buffer ``out``; the
-    tensors as the library reads them (int64 / bool / fp32, contiguous)"""
+    tensors as the library reads them (int64 / bool / fp32, contiguous).
+    out_dtype=torch.uint8: the byte-output twin of either (dctae_decode_u8 /
+    dctae_decode_normed_u8), ``out`` a uint8 buffer in the same layout."""
+    name = ("dctae_decode_normed" if normed else "dctae_decode") + out_dtype_suffix(out_dtype, "decode out_dtype")
+    if out.dtype != out_dtype:
+        raise TypeError(f"{name}: the output buffer is {out.dtype}")
     batch = (ctx.h, C.byref(cfg), table.R, *table.c_args(), ptr(ids), ptr(key_pad), ptr(pos), ptr(ch))
     if normed:
-        rc = ctx.lib.dctae_decode_normed(*batch, C.byref(norm), ptr(patches), ptr(out), _lib.stream_ptr(table.dev))
+        rc = getattr(ctx.lib, name)(*batch, C.byref(norm), ptr(patches), ptr(out), _lib.stream_ptr(table.dev))
     else:
-        rc = ctx.lib.dctae_decode(*batch, C.byref(norm) if norm is not None else None,
-                                  C.byref(lfq) if lfq is not None else None, ptr(codes), ptr(patches), ptr(out),
-                                  _lib.stream_ptr(table.dev))
-    ctx.check(rc, "dctae_decode_normed" if normed else "dctae_decode")
+        rc = getattr(ctx.lib, name)(*batch, C.byref(norm) if norm is not None else None,
+                                    C.byref(lfq) if lfq is not None else None, ptr(codes), ptr(patches), ptr(out),
+                                    _lib.stream_ptr(table.dev))
+    ctx.check(rc, name)
 
 
 def pixel_loss_forward(table: DecodeTable, rgb_hat: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
@@ -729,8 +759,12 @@ def decode(p: FEParams, ids: torch.Tensor, key_pad: torch.Tensor, positions: tor
            patch_sizes: Sequence, original_sizes: Sequence, codes: Optional[torch.Tensor] = None,
            patches: Optional[torch.Tensor] = None, norm: Optional[NormState] = None,
            lfq: Optional[LFQCfg] = None, normed: bool = False, table: Optional[DecodeTable] = None,
-           return_flat: bool = False) -> List[torch.Tensor]:
-    """dctae_decode; returns a list of (3, H, W) fp32 device images.  normed:
+           return_flat: bool = False, out_dtype: torch.dtype = torch.float32) -> List[torch.Tensor]:
+    """dctae_decode; returns a list of (3, H, W) fp32 device images, or with
+    out_dtype=torch.uint8 uint8 images whose every byte is the fp32 call's value
+    through ``x.mul(255).add(0.5).clamp(0, 255).to(torch.uint8)`` (dctae_decode_u8,
+    include/dctae_u8_out.h; torch's allocations keep the flat buffer and so
+    every 512 x 512 image of it 4-byte aligned).  normed:
     patches are PatchNorm outputs and the inverse_norm runs inside the decode
     (dctae_decode_normed; norm required, no codes).  table: the batch's
     DecodeTable when the caller already built it; return_flat: also the flat
@@ -738,13 +772,14 @@ def decode(p: FEParams, ids: torch.Tensor, key_pad: torch.Tensor, positions: tor
     dev = _check_dev(ids, key_pad, positions, channels, codes, patches)
     if table is None:
         table = decode_table(p, ids, key_pad, positions, channels, patch_sizes, original_sizes)
-    out = torch.empty(table.total, dtype=torch.float32, device=dev)
+    out_dtype_suffix(out_dtype, "decode out_dtype")
+    out = torch.empty(table.total, dtype=out_dtype, device=dev)
     cc = codes.long().contiguous() if codes is not None else None
     pp = patches.float().contiguous() if patches is not None else None
     if normed and (norm is None or codes is not None):
         raise AssertionError("normed decode needs the PatchNorm state and patches (no codes)")
     _decode_call(_lib.context(dev), p.c(table.S), table, table.ids, table.key_pad, table.pos, table.ch,
-                 norm.c() if norm is not None else None, lfq, cc, pp, out, normed)
+                 norm.c() if norm is not None else None, lfq, cc, pp, out, normed, out_dtype)
     if normed:
         check_device_errors(dev)
     imgs = table.images(out)

@@ -3,6 +3,7 @@
 // lists the host units.
 #include "dctae_ctx.h"
 #include "../../include/dctae_u8.h"
+#include "../../include/dctae_u8_out.h"
 
 using namespace dctae;
 
@@ -309,6 +310,16 @@ int dctae_u8_to_f32(dctae_ctx* ctx, const uint8_t* x_dev, int64_t n, float* y_de
   if (n == 0) return 0;
   hipSetDevice(ctx->device);
   launch_u8_to_f32(x_dev, n, y_dev, (hipStream_t)stream);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int dctae_f32_to_u8(dctae_ctx* ctx, const float* x_dev, int64_t n, uint8_t* y_dev, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (n < 0 || (n > 0 && (!x_dev || !y_dev))) return fail(ctx, DCTAE_EINVAL, "bad f32_to_u8 args");
+  if (n == 0) return 0;
+  hipSetDevice(ctx->device);
+  launch_f32_to_u8(x_dev, n, y_dev, (hipStream_t)stream);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }

@@ -1,5 +1,7 @@
-// The decode engine: dctae_decode and dctae_decode_normed.
+// The decode engine: dctae_decode and dctae_decode_normed, and their byte-output
+// forms dctae_decode_u8 and dctae_decode_normed_u8 (include/dctae_u8_out.h).
 #include "dctae_ctx.h"
+#include "../../include/dctae_u8_out.h"
 
 using namespace dctae;
 
@@ -105,14 +107,24 @@ DecodeArgs decode_args(const dctae_ctx* ctx, const DecodeBatch& B, const dctae_n
 }  // namespace dctae
 
 // decode of 512 x 512 images on the FFT path: token map -> column DCT-III
-// (tokens expanded in the kernel) -> U -> row DCT-III + IPT -> RGB
+// (tokens expanded in the kernel) -> U -> row DCT-III + IPT -> RGB.
+// rgb / px: the caller's images and their pixel type (ImgDesc::rgb_off in pixels)
 static int decode_fft(OrderedCall& oc, const DecodeBatch& B, std::vector<ImgDesc>& D, const FftPlan& fpl,
                       const dctae_norm* norm, const dctae_lfq* lfq, const int64_t* codes, const float* patches,
-                      float* rgb, bool normed) {
+                      void* rgb, PixelType px, bool normed) {
   dctae_ctx* ctx = oc.ctx;
   const hipStream_t s = oc.s;
   const dctae_fe_cfg* cfg = B.cfg;
   const int n_img = B.n_img;
+  // 32 kept tile columns on the default row kernel: U in the band layout
+  // (k_idct_cols512b); otherwise row-major U (k_idct_cols512)
+  const bool rows512 = ctx->opt.dec_rows_kernel == 3 && D[0].qw == 32;
+  const bool band = rows512 && ctx->opt.dec_cols_kernel == 2;
+  // k_idct_rows512 stores four byte pixels at once (dctae_u8_out.h): refused before any launch
+  for (int i = 0; px == PixelType::kU8 && rows512 && i < n_img; ++i)
+    if (((uintptr_t)rgb + (uintptr_t)D[i].rgb_off) % 4)
+      return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": a 512 x 512 byte image on the 512-wide row "
+                  "kernel must start 4-byte aligned (rgb_dev + out_off[i])");
   int64_t wsf = 0;
   std::vector<int2> rb;
   for (int i = 0; i < n_img; ++i) {
@@ -143,10 +155,6 @@ static int decode_fft(OrderedCall& oc, const DecodeBatch& B, std::vector<ImgDesc
     Timer t(ctx, s, "dec_map");
     launch_dec_map((int64_t)B.n_rows * cfg->max_seq_len, dd, a, map, s);
   }
-  // 32 kept tile columns on the default row kernel: U in the band layout
-  // (k_idct_cols512b); otherwise row-major U (k_idct_cols512)
-  const bool rows512 = ctx->opt.dec_rows_kernel == 3 && D[0].qw == 32;
-  const bool band = rows512 && ctx->opt.dec_cols_kernel == 2;
   {
     Timer t(ctx, s, "idct_cols");
     if (band)
@@ -157,9 +165,9 @@ static int decode_fft(OrderedCall& oc, const DecodeBatch& B, std::vector<ImgDesc
   {
     Timer t(ctx, s, "idct_rows");
     if (rows512)
-      launch_idct_rows512(band, dd, (const int2*)(pd + rb_off), (int)rb.size(), ws, rgb, tw, pre, ctx->cm, s);
+      launch_idct_rows512(band, dd, (const int2*)(pd + rb_off), (int)rb.size(), ws, rgb, px, tw, pre, ctx->cm, s);
     else
-      launch_idct_rows_spec(1, dd, (const int2*)(pd + rb_off), (int)rb.size(), ws, rgb, tw, pre, ctx->cm, s);
+      launch_idct_rows_spec(1, dd, (const int2*)(pd + rb_off), (int)rb.size(), ws, rgb, px, tw, pre, ctx->cm, s);
   }
   HIPCHK(ctx, hipGetLastError());
   return 0;
@@ -168,9 +176,11 @@ static int decode_fft(OrderedCall& oc, const DecodeBatch& B, std::vector<ImgDesc
 // normed: patches are PatchNorm outputs (before inverse_norm); the FFT path
 // applies the inverse in its column kernel (the (c, strip) tables of a block
 // are image-independent), other geometries run dctae_norm_inverse's kernel
-// into the staging buffer first
+// into the staging buffer first.  px: the pixel type of the caller's images
+// (B.out_off in pixels); the tag rides to the kernels that write them, every
+// workspace request, plan entry and launch before them is the same
 static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* norm, const dctae_lfq* lfq,
-                       const int64_t* codes, const float* patches, float* rgb, bool normed) {
+                       const int64_t* codes, const float* patches, void* rgb, PixelType px, bool normed) {
   hipSetDevice(ctx->device);
   const dctae_fe_cfg* cfg = B.cfg;
   const hipStream_t s = B.s;
@@ -210,7 +220,7 @@ static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* n
   if (fftdec) fftdec = fft_plan_for(ctx, 512, P, &fpl) == 0 && fpl.spec == 1;
   OrderedCall oc(ctx, s);
   if (fftdec)
-    return decode_fft(oc, B, D, fpl, norm, lfq, codes, patches, rgb, normed);
+    return decode_fft(oc, B, D, fpl, norm, lfq, codes, patches, rgb, px, normed);
   if (normed && n_rows > 0) {
     // other geometries: the inverse over every packed token into the staging buffer, then as patches
     const int64_t n_tok = (int64_t)n_rows * S;
@@ -271,7 +281,7 @@ static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* n
   }
   {
     Timer t(ctx, s, "ipt_to_rgb");
-    launch_ipt_to_rgb(dd, n_img, max_hw, ws, rgb, ctx->cm, s);
+    launch_ipt_to_rgb(dd, n_img, max_hw, ws, rgb, px, ctx->cm, s);
   }
   HIPCHK(ctx, hipGetLastError());
   return 0;
@@ -287,7 +297,18 @@ int dctae_decode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const 
   const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
                       (hipStream_t)stream};
   if (!ctx) return DCTAE_EINVAL;
-  return decode_impl(ctx, B, norm, lfq, codes, patches, rgb, false);
+  return decode_impl(ctx, B, norm, lfq, codes, patches, rgb, PixelType::kF32, false);
+}
+
+int dctae_decode_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut, int32_t lut_w,
+                    int32_t n_img, const int32_t* out_hw, const int64_t* out_off, const int32_t* patch_hw,
+                    const int64_t* ids, const uint8_t* key_pad, const int64_t* pos, const int64_t* ch,
+                    const dctae_norm* norm, const dctae_lfq* lfq, const int64_t* codes, const float* patches,
+                    uint8_t* rgb, void* stream) {
+  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
+                      (hipStream_t)stream};
+  if (!ctx) return DCTAE_EINVAL;
+  return decode_impl(ctx, B, norm, lfq, codes, patches, rgb, PixelType::kU8, false);
 }
 
 int dctae_decode_normed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut,
@@ -299,7 +320,19 @@ int dctae_decode_normed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows,
                       (hipStream_t)stream};
   if (!ctx) return DCTAE_EINVAL;
   if (n_rows > 0 && !normed_patches) return fail(ctx, DCTAE_EINVAL, "decode needs the PatchNorm-space patches");
-  return decode_impl(ctx, B, norm, nullptr, nullptr, normed_patches, rgb, true);
+  return decode_impl(ctx, B, norm, nullptr, nullptr, normed_patches, rgb, PixelType::kF32, true);
+}
+
+int dctae_decode_normed_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut,
+                           int32_t lut_w, int32_t n_img, const int32_t* out_hw, const int64_t* out_off,
+                           const int32_t* patch_hw, const int64_t* ids, const uint8_t* key_pad, const int64_t* pos,
+                           const int64_t* ch, const dctae_norm* norm, const float* normed_patches, uint8_t* rgb,
+                           void* stream) {
+  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
+                      (hipStream_t)stream};
+  if (!ctx) return DCTAE_EINVAL;
+  if (n_rows > 0 && !normed_patches) return fail(ctx, DCTAE_EINVAL, "decode needs the PatchNorm-space patches");
+  return decode_impl(ctx, B, norm, nullptr, nullptr, normed_patches, rgb, PixelType::kU8, true);
 }
 
 }  // extern "C"

@@ -378,10 +378,12 @@ __global__ __launch_bounds__(256) void k_idct_cols512(const ImgDesc* __restrict_
 // ---------------------------------------------------------------------------
 // rows: one wave = one image row, 3 channels; 16 rows per block.
 //   U[c][y][kx] (kx < Kw, zero beyond) -> conj Z_k -> FFT -> x[px] -> IPT -> RGB
+// Out: the caller's pixel type; one pixel per lane and store (a byte image may
+// start at any byte: a wave's store is 64 contiguous bytes)
 // ---------------------------------------------------------------------------
-template <int N, int R2>
+template <int N, int R2, typename Out>
 __global__ __launch_bounds__(256) void k_idct_rows2(const ImgDesc* __restrict__ imgs, const int2* __restrict__ blocks,
-                                                    const float* __restrict__ ws, float* __restrict__ rgb,
+                                                    const float* __restrict__ ws, Out* __restrict__ rgb,
                                                     const float2* __restrict__ tw, const float4* __restrict__ pre,
                                                     ColorMats cm) {
 #pragma clang fp contract(fast)
@@ -501,7 +503,7 @@ __global__ __launch_bounds__(256) void k_idct_rows2(const ImgDesc* __restrict__ 
     const float* z0 = reinterpret_cast<const float*>(z[0]);
     const float* z1 = reinterpret_cast<const float*>(z[1]);
     const float* z2 = reinterpret_cast<const float*>(z[2]);
-    float* dst = rgb + d.rgb_off + (int64_t)y * N;
+    Out* dst = rgb + d.rgb_off + (int64_t)y * N;
 #pragma unroll
     for (int i = 0; i < PX; ++i) {
       const int px = lane + 64 * i;
@@ -510,9 +512,9 @@ __global__ __launch_bounds__(256) void k_idct_rows2(const ImgDesc* __restrict__ 
         const float l0 = signed_pow_fast(mat3_row(cm.ipt2lms, 0, i0, i1, i2), inv_gamma);
         const float l1 = signed_pow_fast(mat3_row(cm.ipt2lms, 1, i0, i1, i2), inv_gamma);
         const float l2 = signed_pow_fast(mat3_row(cm.ipt2lms, 2, i0, i1, i2), inv_gamma);
-        dst[px] = mat3_row(cm.lms2rgb, 0, l0, l1, l2);
-        dst[hw + px] = mat3_row(cm.lms2rgb, 1, l0, l1, l2);
-        dst[2 * hw + px] = mat3_row(cm.lms2rgb, 2, l0, l1, l2);
+        dst[px] = store_px<Out>(mat3_row(cm.lms2rgb, 0, l0, l1, l2));
+        dst[hw + px] = store_px<Out>(mat3_row(cm.lms2rgb, 1, l0, l1, l2));
+        dst[2 * hw + px] = store_px<Out>(mat3_row(cm.lms2rgb, 2, l0, l1, l2));
       }
     }
   }
@@ -651,13 +653,25 @@ void launch_idct_cols512(const ImgDesc* imgs, int n_img, int qw, float* ws, cons
                        pre, a);
 }
 
-void launch_idct_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws,
-                           float* rgb, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s) {
-  if (n_blocks <= 0) return;
+template <typename Out>
+static void launch_idct_rows_spec_as(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws,
+                                     Out* rgb, const float2* tw, const float4* pre, const ColorMats& cm,
+                                     hipStream_t s) {
   if (spec == 1)
-    hipLaunchKernelGGL((k_idct_rows2<512, 16>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, rgb, tw, pre, cm);
+    hipLaunchKernelGGL((k_idct_rows2<512, 16, Out>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, rgb, tw, pre,
+                       cm);
   else if (spec == 2)
-    hipLaunchKernelGGL((k_idct_rows2<224, 7>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, rgb, tw, pre, cm);
+    hipLaunchKernelGGL((k_idct_rows2<224, 7, Out>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, rgb, tw, pre,
+                       cm);
+}
+
+void launch_idct_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, void* rgb,
+                           PixelType px, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s) {
+  if (n_blocks <= 0) return;
+  if (px == PixelType::kU8)
+    launch_idct_rows_spec_as(spec, imgs, blocks, n_blocks, ws, (uint8_t*)rgb, tw, pre, cm, s);
+  else
+    launch_idct_rows_spec_as(spec, imgs, blocks, n_blocks, ws, (float*)rgb, tw, pre, cm, s);
 }
 
 }  // namespace dctae

@@ -17,6 +17,10 @@
 //  * pass 1 in registers -> ONE LDS transpose -> pass 2: lane j holds W[j + 16 r];
 //  * output pixels 64 b + 4 j .. + 3 of block b: (Re W[b], -Im W'[15-b],
 //    -Im W[b], Re W'[15-b]) with W' the mirror lane's: 16-byte stores.
+// Out = uint8_t (dctae_u8_out.h): the same values through byte_from_unit, four
+// pixels of a lane = one dword; the dwords of four blocks b are transposed
+// across the lanes of a quad (xpose4_quad), so lane j = 4 jq + jr stores the 16
+// bytes 64 (4 bb + jr) + 16 jq .. + 15 of the row: 6 stores per lane, not 24.
 #include "dctae_device.h"
 #include "dctae_fft_common.h"
 #include "dctae_launch.h"
@@ -33,6 +37,27 @@ __device__ __forceinline__ float iror16(float x) {      // lane l <- lane l - 1 
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x121, 0xf, 0xf, false));
 }
 
+// 4 x 4 transpose across the four lanes of a quad: on return r[k] at lane
+// 4 q + l holds the input r[l] of lane 4 q + k.  Two 2 x 2 block exchanges
+// (lane ^ 1, then lane ^ 2) by DPP quad_perm: VALU only, no LDS.
+__device__ __forceinline__ void xpose4_quad(uint32_t (&r)[4], int lane) {
+  const bool p1 = lane & 1, p2 = lane & 2;
+#pragma unroll
+  for (int a = 0; a < 4; a += 2) {   // registers (a, a + 1) with lane ^ 1: quad_perm [1, 0, 3, 2]
+    const uint32_t send = p1 ? r[a] : r[a + 1];
+    const uint32_t got = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, 0xB1, 0xf, 0xf, false);
+    r[a] = p1 ? got : r[a];
+    r[a + 1] = p1 ? r[a + 1] : got;
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {      // registers (a, a + 2) with lane ^ 2: quad_perm [2, 3, 0, 1]
+    const uint32_t send = p2 ? r[a] : r[a + 2];
+    const uint32_t got = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, 0x4E, 0xf, 0xf, false);
+    r[a] = p2 ? got : r[a];
+    r[a + 2] = p2 ? r[a + 2] : got;
+  }
+}
+
 constexpr int kIXchStride = 528;   // the two row groups of a half-wave on opposite bank halves
 
 struct IRows512Lds {
@@ -45,10 +70,11 @@ struct IRows512Lds {
 
 // BAND: U in the band layout U' of k_idct_cols512b (element (y, kx) at
 // u4_index(y / 4, kx) * 4 + y % 4); otherwise row-major
-// U[c][y][kx] (k_idct_cols512)
-template <int KW, bool BAND>
+// U[c][y][kx] (k_idct_cols512).  Out: the caller's pixel type (float, or
+// uint8_t with the image base 4-byte aligned), ImgDesc::rgb_off in pixels
+template <int KW, bool BAND, typename Out>
 __global__ __launch_bounds__(256) void k_idct_rows512(const ImgDesc* __restrict__ imgs, const int2* __restrict__ blocks,
-                                                      const float* __restrict__ ws, float* __restrict__ rgb,
+                                                      const float* __restrict__ ws, Out* __restrict__ rgb,
                                                       const float2* __restrict__ tw, const float4* __restrict__ pre,
                                                       ColorMats cm) {
 #pragma clang fp contract(fast)
@@ -181,13 +207,11 @@ __global__ __launch_bounds__(256) void k_idct_rows512(const ImgDesc* __restrict_
   if (y >= H) return;
   const float inv_gamma = 2.3255813121795654296875f;   // fp32(1/0.43), util.py:93
   const int64_t hw = (int64_t)H * N;
-  float* dst = rgb + d.rgb_off + (int64_t)y * N + 4 * j;
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
+  // o[c][e] = channel c of pixel 64 b + 4 j + e
+  auto rgb4 = [&](int b, float (&o)[3][4]) {
     const float* i0 = reinterpret_cast<const float*>(&X[0][b]);
     const float* i1 = reinterpret_cast<const float*>(&X[1][b]);
     const float* i2 = reinterpret_cast<const float*>(&X[2][b]);
-    float o[3][4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float l0 = signed_pow_fast(mat3_row(cm.ipt2lms, 0, i0[e], i1[e], i2[e]), inv_gamma);
@@ -197,20 +221,56 @@ __global__ __launch_bounds__(256) void k_idct_rows512(const ImgDesc* __restrict_
       o[1][e] = mat3_row(cm.lms2rgb, 1, l0, l1, l2);
       o[2][e] = mat3_row(cm.lms2rgb, 2, l0, l1, l2);
     }
+  };
+  if constexpr (sizeof(Out) == 4) {
+    float* dst = rgb + d.rgb_off + (int64_t)y * N + 4 * j;
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
-      *reinterpret_cast<float4*>(dst + c * hw + 64 * b) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+    for (int b = 0; b < 8; ++b) {
+      float o[3][4];
+      rgb4(b, o);
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        *reinterpret_cast<float4*>(dst + c * hw + 64 * b) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+    }
+  } else {
+    uint8_t* dst = rgb + d.rgb_off + (int64_t)y * N + 64 * (j & 3) + 16 * (j >> 2);
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb) {
+      uint32_t w[3][4];   // [c][k]: the lane's dword of block 4 bb + k
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float o[3][4];
+        rgb4(4 * bb + k, o);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) w[c][k] = dword_from_units(o[c]);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        xpose4_quad(w[c], j);   // w[c][k]: the dword of lane 4 (j / 4) + k in block 4 bb + j % 4
+        *reinterpret_cast<uint4*>(dst + c * hw + 256 * bb) = make_uint4(w[c][0], w[c][1], w[c][2], w[c][3]);
+      }
+    }
   }
 }
 
-void launch_idct_rows512(bool band, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, float* rgb,
-                         const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s) {
-  if (n_blocks <= 0) return;
+template <typename Out>
+static void launch_idct_rows512_as(bool band, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws,
+                                   Out* rgb, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s) {
   if (band)
-    hipLaunchKernelGGL((k_idct_rows512<448, true>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, rgb, tw, pre, cm);
+    hipLaunchKernelGGL((k_idct_rows512<448, true, Out>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, rgb, tw,
+                       pre, cm);
   else
-    hipLaunchKernelGGL((k_idct_rows512<448, false>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, rgb, tw, pre,
-                       cm);
+    hipLaunchKernelGGL((k_idct_rows512<448, false, Out>), dim3(n_blocks), dim3(256), 0, s, imgs, blocks, ws, rgb, tw,
+                       pre, cm);
+}
+
+void launch_idct_rows512(bool band, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, void* rgb,
+                         PixelType px, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s) {
+  if (n_blocks <= 0) return;
+  if (px == PixelType::kU8)
+    launch_idct_rows512_as(band, imgs, blocks, n_blocks, ws, (uint8_t*)rgb, tw, pre, cm, s);
+  else
+    launch_idct_rows512_as(band, imgs, blocks, n_blocks, ws, (float*)rgb, tw, pre, cm, s);
 }
 
 }  // namespace dctae

@@ -225,13 +225,27 @@ void launch_u8_to_f32(const uint8_t* x, int64_t n, float* y, hipStream_t s) {
   hipLaunchKernelGGL(k_u8_to_f32, dim3(g), dim3(256), 0, s, x, n, y);
 }
 
-// ipt (3,H,W) in place -> rgb written to out (3,H,W)
+// the inverse twin (dctae_f32_to_u8): y[i] = byte_from_unit(x[i]), byte stores at any alignment
+__global__ __launch_bounds__(256) void k_f32_to_u8(const float* __restrict__ x, int64_t n, uint8_t* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    y[i] = byte_from_unit(x[i]);
+}
+
+void launch_f32_to_u8(const float* x, int64_t n, uint8_t* y, hipStream_t s) {
+  if (n <= 0) return;
+  const int g = (int)std::min<int64_t>((n + 255) / 256, 1 << 16);
+  hipLaunchKernelGGL(k_f32_to_u8, dim3(g), dim3(256), 0, s, x, n, y);
+}
+
+// ipt (3,H,W) in place -> rgb written to out (3,H,W), one pixel per store (a
+// byte image may start at any byte)
+template <typename Out>
 __global__ void k_ipt_to_rgb(const ImgDesc* __restrict__ imgs, const float* __restrict__ ws,
-                             float* __restrict__ out, ColorMats cm) {
+                             Out* __restrict__ out, ColorMats cm) {
   const ImgDesc d = imgs[blockIdx.y];
   const int64_t hw = (int64_t)d.H * d.W;
   const float* src = ws + d.ws_p;
-  float* dst = out + d.rgb_off;
+  Out* dst = out + d.rgb_off;
   const float inv_gamma = 2.3255813121795654296875f;  // fp32(1/0.43)
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < hw;
        e += (int64_t)gridDim.x * blockDim.x) {
@@ -239,16 +253,19 @@ __global__ void k_ipt_to_rgb(const ImgDesc* __restrict__ imgs, const float* __re
     float l0 = signed_pow(mat3_row(cm.ipt2lms, 0, i0, i1, i2), inv_gamma);
     float l1 = signed_pow(mat3_row(cm.ipt2lms, 1, i0, i1, i2), inv_gamma);
     float l2 = signed_pow(mat3_row(cm.ipt2lms, 2, i0, i1, i2), inv_gamma);
-    dst[e] = mat3_row(cm.lms2rgb, 0, l0, l1, l2);
-    dst[hw + e] = mat3_row(cm.lms2rgb, 1, l0, l1, l2);
-    dst[2 * hw + e] = mat3_row(cm.lms2rgb, 2, l0, l1, l2);
+    dst[e] = store_px<Out>(mat3_row(cm.lms2rgb, 0, l0, l1, l2));
+    dst[hw + e] = store_px<Out>(mat3_row(cm.lms2rgb, 1, l0, l1, l2));
+    dst[2 * hw + e] = store_px<Out>(mat3_row(cm.lms2rgb, 2, l0, l1, l2));
   }
 }
 
-void launch_ipt_to_rgb(const ImgDesc* imgs, int n_img, int64_t max_hw, const float* ws, float* out,
+void launch_ipt_to_rgb(const ImgDesc* imgs, int n_img, int64_t max_hw, const float* ws, void* out, PixelType px,
                        const ColorMats& cm, hipStream_t s) {
   int gx = (int)std::min<int64_t>((max_hw + 255) / 256, 1024);
-  hipLaunchKernelGGL(k_ipt_to_rgb, dim3(gx, n_img), dim3(256), 0, s, imgs, ws, out, cm);
+  if (px == PixelType::kU8)
+    hipLaunchKernelGGL(k_ipt_to_rgb<uint8_t>, dim3(gx, n_img), dim3(256), 0, s, imgs, ws, (uint8_t*)out, cm);
+  else
+    hipLaunchKernelGGL(k_ipt_to_rgb<float>, dim3(gx, n_img), dim3(256), 0, s, imgs, ws, (float*)out, cm);
 }
 
 // colour transform of a contiguous batch of (3, H, W) images, out of place:

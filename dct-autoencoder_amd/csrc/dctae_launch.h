@@ -17,7 +17,10 @@ void launch_rgb_to_ipt(const ImgDesc* imgs, const int2* blocks, int n_blocks, co
                        const ColorMats& cm, uint32_t* amax, hipStream_t s);
 // y[i] = x[i] / 255 (unit_from_byte), n elements
 void launch_u8_to_f32(const uint8_t* x, int64_t n, float* y, hipStream_t s);
-void launch_ipt_to_rgb(const ImgDesc* imgs, int n_img, int64_t max_hw, const float* ws, float* out,
+// y[i] = byte_from_unit(x[i]), n elements
+void launch_f32_to_u8(const float* x, int64_t n, uint8_t* y, hipStream_t s);
+// out / px (here and in the decode's row-pass launchers): the caller's image buffer and its pixel type
+void launch_ipt_to_rgb(const ImgDesc* imgs, int n_img, int64_t max_hw, const float* ws, void* out, PixelType px,
                        const ColorMats& cm, hipStream_t s);
 void launch_color(const float* x, float* y, int64_t hw, int n_img, int dir, const ColorMats& cm, hipStream_t s);
 // amax (nullable): [2 i + 1] receives the |max| bits of the folded T (k_gemm_h2)
@@ -157,11 +160,12 @@ void launch_idct_cols512b(const ImgDesc* imgs, int n_img, float* ws, const int32
                           const float4* pre, const DecodeArgs& a, hipStream_t s);
 void launch_idct_cols512(const ImgDesc* imgs, int n_img, int qw, float* ws, const int32_t* map, const float2* tw,
                          const float4* pre, const DecodeArgs& a, hipStream_t s);
-void launch_idct_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws,
-                           float* rgb, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s);
+void launch_idct_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, void* rgb,
+                           PixelType px, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s);
 
-void launch_idct_rows512(bool band, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, float* rgb,
-                         const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s);
+// px = kU8: four pixels per store, every image's base 4-byte aligned (decode_fft refuses otherwise)
+void launch_idct_rows512(bool band, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, void* rgb,
+                         PixelType px, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s);
 void launch_rows512(const ImgDesc* imgs, const int2* blocks, int n_blocks, const void* rgb, PixelType px, float* ws,
                     const float2* tw, const float2* post, const ColorMats& cm, hipStream_t s);
 

@@ -364,7 +364,7 @@ class DCTAutoencoderFeatureExtractor:
                 images.append(img)
         return images
 
-    def postprocess(self, x: DCTPatches) -> List[torch.Tensor]:
+    def postprocess(self, x: DCTPatches, output_dtype: torch.dtype = torch.float32) -> List[torch.Tensor]:
         """FE:289-310: un-normalised DCTPatches -> RGB images (revert_patching,
         zero pad, DCT-III, IPT -> RGB fused on the GPU).  With an overridden
         _transform_image_out / revert_patching the reference's stage sequence
@@ -374,25 +374,35 @@ class DCTAutoencoderFeatureExtractor:
         enabled) give the same images, bit for bit, with a grad_fn whose
         backward is dctae_decode_backward; fp16 / bf16 patches are upcast to
         fp32 and the gradient is cast back.  The staged-hook path stays
-        without a grad_fn."""
-        if x.patches.requires_grad and torch.is_grad_enabled() and x.patches.is_cuda and not self._staged_out():
+        without a grad_fn.
+
+        output_dtype=torch.uint8: uint8 images written by the decode itself
+        (dctae_decode_u8), every byte the fp32 image's value through
+        ``x.mul(255).add(0.5).clamp(0, 255).to(torch.uint8)`` (save_image's
+        rounding).  Bytes carry no grad_fn: patches that require grad take the
+        no-grad path.  With overridden hooks the stages run in fp32 and each
+        hook result is converted by dctae_f32_to_u8."""
+        _ops.out_dtype_suffix(output_dtype, "postprocess output_dtype")
+        if (output_dtype == torch.float32 and x.patches.requires_grad and torch.is_grad_enabled()
+                and x.patches.is_cuda and not self._staged_out()):
             from . import losses
             return losses.differentiable_postprocess(self, x)
-        return self._postprocess_no_grad(x)
+        return self._postprocess_no_grad(x, output_dtype)
 
     @torch.no_grad()
-    def _postprocess_no_grad(self, x: DCTPatches) -> List[torch.Tensor]:
+    def _postprocess_no_grad(self, x: DCTPatches, output_dtype: torch.dtype = torch.float32) -> List[torch.Tensor]:
         if self._staged_out():
             images = []
             for image, (h, w) in zip(self.revert_patching(x), x.original_sizes):
                 ch, cw = image.shape[-2:]
                 im_pad = torch.zeros(self.channels, h, w, device=image.device, dtype=image.dtype)
                 im_pad[:, :ch, :cw] = image
-                images.append(self._transform_image_out(im_pad))
+                im = self._transform_image_out(im_pad)
+                images.append(_ops.f32_to_u8(im.float()) if output_dtype == torch.uint8 else im)
             return images
         return _ops.decode(self.params(x.patches.shape[1]), x.batched_image_ids, x.key_pad_mask,
                            x.patch_positions, x.patch_channels, x.patch_sizes, x.original_sizes,
-                           patches=x.patches)
+                           patches=x.patches, out_dtype=output_dtype)
 
     # ------------------------------------------------------- fused MI355X path
     @torch.no_grad()
@@ -519,11 +529,14 @@ class DCTAutoencoderFeatureExtractor:
                           len(idx))   # Images or ImagesU8, as the call's descriptor
 
     @torch.no_grad()
-    def decode_batch(self, dct_patches: DCTPatches, codes: torch.Tensor, patchnorm, lfq) -> List[torch.Tensor]:
+    def decode_batch(self, dct_patches: DCTPatches, codes: torch.Tensor, patchnorm, lfq,
+                     output_dtype: torch.dtype = torch.float32) -> List[torch.Tensor]:
         """LFQ.indices_to_codes -> PatchNorm.inverse_norm -> postprocess, fused
         (the decode half of SURVEY §3.4 without the transformer).  With LFQ
         projections the codes go through the fused codes -> project_out kernel and the HIP
-        inverse PatchNorm first, and the fused decode starts from the tokens."""
+        inverse PatchNorm first, and the fused decode starts from the tokens.
+        output_dtype=torch.uint8: uint8 images, as postprocess gives them."""
+        _ops.out_dtype_suffix(output_dtype, "decode_batch output_dtype")
         staged = self._staged_out()   # an overridden revert_patching / _transform_image_out (FE:289-310)
         if lfq.has_projections or staged:
             dp = dct_patches.shallow_copy()
@@ -534,15 +547,16 @@ class DCTAutoencoderFeatureExtractor:
                 x = _ops.lfq_project_out(codes, w, b, lfq.cfg())
                 return _ops.decode(self.params(dp.key_pad_mask.shape[1]), dp.batched_image_ids, dp.key_pad_mask,
                                    dp.patch_positions, dp.patch_channels, dp.patch_sizes, dp.original_sizes,
-                                   patches=x, norm=patchnorm.state(thresholds=False), normed=True)
+                                   patches=x, norm=patchnorm.state(thresholds=False), normed=True,
+                                   out_dtype=output_dtype)
             else:
                 dp.patches = lfq.indices_to_codes(codes)
                 dp.patches = patchnorm.inverse_norm(dp)
-            return self.postprocess(dp)
+            return self.postprocess(dp, output_dtype)
         return _ops.decode(self.params(dct_patches.key_pad_mask.shape[1]), dct_patches.batched_image_ids,
                            dct_patches.key_pad_mask, dct_patches.patch_positions, dct_patches.patch_channels,
                            dct_patches.patch_sizes, dct_patches.original_sizes, codes=codes,
-                           norm=patchnorm.state(), lfq=lfq.cfg())
+                           norm=patchnorm.state(), lfq=lfq.cfg(), out_dtype=output_dtype)
 
 
 class BatchEncoder:
@@ -648,9 +662,14 @@ class BatchDecoder:
     round trip): LFQ.indices_to_codes -> PatchNorm.inverse_norm ->
     revert_patching -> IDCT -> IPT -> RGB of the encoder's packed outputs
     (dctae_decode), images in the reference's enumeration order (rows in
-    order, image ids ascending, FE:619-633) into one (B, 3, H, W) tensor."""
+    order, image ids ascending, FE:619-633) into one (B, 3, H, W) tensor.
+    output_dtype=torch.uint8: ``out`` is a (B, 3, H, W) uint8 tensor written by
+    the decode itself (dctae_decode_u8 / dctae_decode_normed_u8), every byte the
+    fp32 decoder's value through ``mul(255).add(0.5).clamp(0, 255)`` truncated."""
 
-    def __init__(self, enc: "BatchEncoder", patchnorm, lfq):
+    def __init__(self, enc: "BatchEncoder", patchnorm, lfq, output_dtype: torch.dtype = torch.float32):
+        _ops.out_dtype_suffix(output_dtype, "BatchDecoder output_dtype")
+        self.output_dtype = output_dtype
         self.enc = enc
         pl, p = enc.plan, enc.fe.patch_size
         self.table = _ops.DecodeTable.from_layout(enc.p, enc.dev, enc.n_rows, enc.S, pl.row, pl.local_id,
@@ -665,12 +684,13 @@ class BatchDecoder:
         # of a per-token table gather); False: project_out with the inverse fused
         # (dctae_lfq_project_out_inverse_norm), then dctae_decode
         self.normed_decode = True
-        self.out = torch.empty((enc.B, 3, enc.H, enc.W), dtype=torch.float32, device=enc.dev)
+        self.out = torch.empty((enc.B, 3, enc.H, enc.W), dtype=output_dtype, device=enc.dev)
 
     def _decode(self, packed, norm, lcfg, codes, patches, normed=False) -> torch.Tensor:
         e = self.enc
         _ops._decode_call(e.ctx, e._cfg, self.table, packed["image_ids"], packed["key_pad_mask"],
-                          packed["positions"], packed["channels"], norm, lcfg, codes, patches, self.out, normed)
+                          packed["positions"], packed["channels"], norm, lcfg, codes, patches, self.out, normed,
+                          self.output_dtype)
         return self.out
 
     def __call__(self, packed) -> torch.Tensor:
