@@ -66,6 +66,11 @@ class PackedOut(C.Structure):
                 ("raw_patches_dev", C.c_void_p), ("scores_dev", C.c_void_p)]
 
 
+class PackedOut16(C.Structure):
+    """dctae_packed_out16 (include/dctae_codes16.h): codes_dev points at int16"""
+    _fields_ = PackedOut._fields_
+
+
 class VQCfg(C.Structure):
     _fields_ = [("dim", C.c_int32), ("heads", C.c_int32), ("codebook_dim", C.c_int32),
                 ("codebook_size", C.c_int32), ("affine", C.c_int32), ("affine_decay", C.c_float),
@@ -150,6 +155,27 @@ _SIGS = {
                                 C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P,
                                 C.POINTER(Norm), _P, _P, _P], C.c_int),
     "dctae_f32_to_u8": ([_P, _P, C.c_int64, _P, _P], C.c_int),
+    # include/dctae_codes16.h: the int16-code entries (their twins' arguments, the code pointer's type apart)
+    "dctae_encode_c16": ([_P, C.POINTER(FECfg), C.POINTER(Images), C.POINTER(Packing), C.POINTER(Norm),
+                          C.POINTER(LFQCfg), C.POINTER(PackedOut16), _P], C.c_int),
+    "dctae_encode_u8_c16": ([_P, C.POINTER(FECfg), C.POINTER(ImagesU8), C.POINTER(Packing), C.POINTER(Norm),
+                             C.POINTER(LFQCfg), C.POINTER(PackedOut16), _P], C.c_int),
+    "dctae_encode_lfq_proj_c16": ([_P, C.POINTER(FECfg), C.POINTER(Images), C.POINTER(Packing), C.POINTER(Norm),
+                                   C.POINTER(LFQCfg), _P, _P, C.POINTER(PackedOut16), _P], C.c_int),
+    "dctae_encode_lfq_proj_u8_c16": ([_P, C.POINTER(FECfg), C.POINTER(ImagesU8), C.POINTER(Packing), C.POINTER(Norm),
+                                      C.POINTER(LFQCfg), _P, _P, C.POINTER(PackedOut16), _P], C.c_int),
+    "dctae_decode_c16": ([_P, C.POINTER(FECfg), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                          C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P,
+                          C.POINTER(Norm), C.POINTER(LFQCfg), _P, _P, _P, _P], C.c_int),
+    "dctae_decode_u8_c16": ([_P, C.POINTER(FECfg), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                             C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P,
+                             C.POINTER(Norm), C.POINTER(LFQCfg), _P, _P, _P, _P], C.c_int),
+    "dctae_lfq_project_in_c16": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, C.c_int32, _P, _P, _P, _P], C.c_int),
+    "dctae_lfq_project_in_bounded_c16": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, C.c_int32, _P, _P, C.c_float, _P, _P],
+                                         C.c_int),
+    "dctae_lfq_project_out_c16": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, C.c_int32, _P, _P, _P, _P], C.c_int),
+    "dctae_lfq_project_out_inverse_norm_c16": ([_P, C.POINTER(LFQCfg), _P, C.c_int64, C.c_int32, _P, _P,
+                                                C.POINTER(Norm), C.c_int32, C.c_int32, _P, _P, _P, _P], C.c_int),
     "dctae_decode_backward": ([_P, C.POINTER(FECfg), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P, _P, _P, _P,
                                _P, _P, _P, _P, _P, _P, _P], C.c_int),

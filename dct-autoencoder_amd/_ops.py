@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import FECfg, Images, ImagesU8, LFQCfg, Norm, PackedOut, Packing, VQCfg, i32, i64, ptr
+from ._lib import FECfg, Images, ImagesU8, LFQCfg, Norm, PackedOut, PackedOut16, Packing, VQCfg, i32, i64, ptr
 
 
 @dataclass(frozen=True)
@@ -189,6 +189,33 @@ def out_dtype_suffix(dtype: torch.dtype, what: str) -> str:
     raise TypeError(f"{what}: torch.float32 or torch.uint8, got {dtype}")
 
 
+def codes_dtype_suffix(dtype: torch.dtype, what: str) -> str:
+    """the entry-point suffix of a code dtype: "" (int64) or "_c16" (int16,
+    include/dctae_codes16.h: an int16 code c means the int64 code int64(c));
+    anything else is a TypeError naming ``what``"""
+    if dtype == torch.int64:
+        return ""
+    if dtype == torch.int16:
+        return "_c16"
+    raise TypeError(f"{what}: torch.int64 or torch.int16, got {dtype}")
+
+
+def check_codes16(cfg: LFQCfg, what: str):
+    """int16 codes hold codebook_dim <= 15 bits (include/dctae_codes16.h)"""
+    if cfg.codebook_dim > 15:
+        raise ValueError(f"{what}: int16 codes hold codebook_dim <= 15 bits, got codebook_dim = {cfg.codebook_dim}")
+
+
+def codes_in(codes: torch.Tensor, cfg: Optional[LFQCfg], what: str):
+    """codes as a kernel reads them, and their entry-point suffix: int16 as it
+    is (the ``_c16`` entries, no widened copy), anything else as int64"""
+    if codes.dtype == torch.int16:
+        if cfg is not None:
+            check_codes16(cfg, what)
+        return codes.contiguous(), "_c16"
+    return codes.long().contiguous(), ""
+
+
 def f32_to_u8(x: torch.Tensor) -> torch.Tensor:
     """dctae_f32_to_u8: the uint8 tensor of an fp32 device tensor by the byte
     decode's rule, ``x.mul(255).add(0.5).clamp(0, 255).to(torch.uint8)`` as
@@ -205,8 +232,13 @@ def f32_to_u8(x: torch.Tensor) -> torch.Tensor:
 
 def encode(imgs_desc: Images, dev: torch.device, p: FEParams, plan, n_rows: int, seq_len: int,
            norm: Optional[NormState], lfq: Optional[LFQCfg], want_codes=True, want_patches=False,
-           want_raw=False, want_scores=False, out=None):
-    """dctae_encode (dctae_encode_u8 for an ImagesU8 descriptor): returns dict of packed device tensors."""
+           want_raw=False, want_scores=False, out=None, codes_dtype: torch.dtype = torch.int64):
+    """dctae_encode (dctae_encode_u8 for an ImagesU8 descriptor): returns dict of packed device tensors.
+    codes_dtype=torch.int16: the codes as int16 (dctae_encode_c16 / dctae_encode_u8_c16), each the int64
+    call's code converted; every other output the same."""
+    c16 = codes_dtype_suffix(codes_dtype, "encode codes_dtype") if want_codes else ""
+    if c16:
+        check_codes16(lfq, "encode")
     ctx = _lib.context(dev)
     S = seq_len
     PP = p.patch_size ** 2
@@ -224,7 +256,7 @@ def encode(imgs_desc: Images, dev: torch.device, p: FEParams, plan, n_rows: int,
         "key_pad_mask": alloc("key_pad_mask", (n_rows, S), torch.bool),
     }
     if want_codes:
-        res["codes"] = alloc("codes", (n_rows, S, lfq.num_codebooks), torch.long)
+        res["codes"] = alloc("codes", (n_rows, S, lfq.num_codebooks), codes_dtype)
     if want_patches:
         res["patches"] = alloc("patches", (n_rows, S, PP), torch.float32)
     if want_raw:
@@ -233,10 +265,10 @@ def encode(imgs_desc: Images, dev: torch.device, p: FEParams, plan, n_rows: int,
         res["scores"] = alloc("scores", (n_rows, S), torch.float32)
     pk_keep = [i32(plan.row), i32(plan.col), i32(plan.k), i32(plan.local_id), i32(plan.row_len)]
     pk = Packing(*[C.cast(a, C.POINTER(C.c_int32)) for a in pk_keep], n_rows)
-    po = PackedOut(ptr(res.get("codes")), ptr(res["positions"]), ptr(res["channels"]), ptr(res["image_ids"]),
+    po = (PackedOut16 if c16 else PackedOut)(ptr(res.get("codes")), ptr(res["positions"]), ptr(res["channels"]), ptr(res["image_ids"]),
                    ptr(res["key_pad_mask"]), ptr(res.get("patches")), ptr(res.get("raw")), ptr(res.get("scores")))
     nc = norm.c() if norm is not None else None
-    name = "dctae_encode_u8" if isinstance(imgs_desc, ImagesU8) else "dctae_encode"
+    name = ("dctae_encode_u8" if isinstance(imgs_desc, ImagesU8) else "dctae_encode") + c16
     rc = getattr(ctx.lib, name)(ctx.h, C.byref(p.c(S)), C.byref(imgs_desc), C.byref(pk),
                                 C.byref(nc) if nc is not None else None,
                                 C.byref(lfq) if lfq is not None else None, C.byref(po), _lib.stream_ptr(dev))
@@ -513,49 +545,56 @@ def lfq_codes(idx: torch.Tensor, cfg: LFQCfg) -> torch.Tensor:
 
 
 def lfq_project_in(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], cfg: LFQCfg,
-                   x_bound: Optional[float] = None) -> torch.Tensor:
+                   x_bound: Optional[float] = None, codes_dtype: torch.dtype = torch.int64) -> torch.Tensor:
     """LFQ.forward's indices with project_in fused (dctae_lfq_project_in):
     x (..., dim) -> (..., num_codebooks) int64.  w / b: project_in's fp32
     weight (ncb*cd, dim) and bias on x's device.  x_bound: the caller's bound
-    |x| <= x_bound (dctae_lfq_project_in_bounded: the fp16 kernels)."""
-    return lfq_project_in_into(x, w, b, cfg, None, x_bound)
+    |x| <= x_bound (dctae_lfq_project_in_bounded: the fp16 kernels).
+    codes_dtype=torch.int16: int16 indices (dctae_lfq_project_in_c16 /
+    dctae_lfq_project_in_bounded_c16), each the int64 call's index converted."""
+    return lfq_project_in_into(x, w, b, cfg, None, x_bound, codes_dtype)
 
 
 def lfq_project_in_into(x, w, b, cfg: LFQCfg, idx: Optional[torch.Tensor],
-                        x_bound: Optional[float] = None) -> torch.Tensor:
+                        x_bound: Optional[float] = None, codes_dtype: torch.dtype = torch.int64) -> torch.Tensor:
+    c16 = codes_dtype_suffix(codes_dtype, "project_in codes_dtype")
+    if c16:
+        check_codes16(cfg, "project_in")
     dev = _check_dev(x, w, b)
     ctx = _lib.context(dev)
     xs = x.float().contiguous()
     dim = xs.shape[-1]
     n = xs.numel() // dim
     shape = (*xs.shape[:-1], cfg.num_codebooks)
-    if idx is None or idx.shape != shape or idx.dtype != torch.long or not idx.is_contiguous() or idx.device != dev:
-        idx = torch.empty(shape, dtype=torch.long, device=dev)
+    if idx is None or idx.shape != shape or idx.dtype != codes_dtype or not idx.is_contiguous() or idx.device != dev:
+        idx = torch.empty(shape, dtype=codes_dtype, device=dev)
     if x_bound is not None:
-        rc = ctx.lib.dctae_lfq_project_in_bounded(ctx.h, C.byref(cfg), ptr(xs), n, dim, ptr(w), ptr(b),
-                                                  float(x_bound), ptr(idx), _lib.stream_ptr(dev))
-        ctx.check(rc, "dctae_lfq_project_in_bounded")
+        name = "dctae_lfq_project_in_bounded" + c16
+        rc = getattr(ctx.lib, name)(ctx.h, C.byref(cfg), ptr(xs), n, dim, ptr(w), ptr(b), float(x_bound), ptr(idx),
+                                    _lib.stream_ptr(dev))
+        ctx.check(rc, name)
         return idx
-    rc = ctx.lib.dctae_lfq_project_in(ctx.h, C.byref(cfg), ptr(xs), n, dim, ptr(w), ptr(b), ptr(idx),
-                                      _lib.stream_ptr(dev))
-    ctx.check(rc, "dctae_lfq_project_in")
+    name = "dctae_lfq_project_in" + c16
+    rc = getattr(ctx.lib, name)(ctx.h, C.byref(cfg), ptr(xs), n, dim, ptr(w), ptr(b), ptr(idx), _lib.stream_ptr(dev))
+    ctx.check(rc, name)
     return idx
 
 
 def lfq_project_out(idx: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], cfg: LFQCfg) -> torch.Tensor:
     """LFQ.indices_to_codes with project_out fused (dctae_lfq_project_out):
-    idx (..., num_codebooks) -> (..., dim) fp32; w (dim, ncb*cd), b (dim)."""
+    idx (..., num_codebooks) -> (..., dim) fp32; w (dim, ncb*cd), b (dim).
+    int16 indices are read as they are (dctae_lfq_project_out_c16)."""
     dev = _check_dev(idx, w, b)
     ctx = _lib.context(dev)
-    ii = idx.long().contiguous()
+    ii, c16 = codes_in(idx, cfg, "project_out")
     if ii.shape[-1] != cfg.num_codebooks:
         raise AssertionError("last dim of indices must be num_codebooks")
     dim = w.shape[0]
     n = ii.numel() // cfg.num_codebooks
     out = torch.empty((*ii.shape[:-1], dim), dtype=torch.float32, device=dev)
-    rc = ctx.lib.dctae_lfq_project_out(ctx.h, C.byref(cfg), ptr(ii), n, dim, ptr(w), ptr(b), ptr(out),
-                                       _lib.stream_ptr(dev))
-    ctx.check(rc, "dctae_lfq_project_out")
+    name = "dctae_lfq_project_out" + c16
+    rc = getattr(ctx.lib, name)(ctx.h, C.byref(cfg), ptr(ii), n, dim, ptr(w), ptr(b), ptr(out), _lib.stream_ptr(dev))
+    ctx.check(rc, name)
     return out
 
 
@@ -563,10 +602,11 @@ def lfq_project_out_inverse_norm(idx: torch.Tensor, w: torch.Tensor, b: Optional
                                  norm: NormState, p: FEParams, channels: torch.Tensor,
                                  positions: torch.Tensor) -> torch.Tensor:
     """LFQ.indices_to_codes (project_out) + PatchNorm.inverse_norm in one kernel
-    (dctae_lfq_project_out_inverse_norm): idx (..., ncb) -> (..., P*P) fp32."""
+    (dctae_lfq_project_out_inverse_norm): idx (..., ncb) -> (..., P*P) fp32.
+    int16 indices are read as they are (dctae_lfq_project_out_inverse_norm_c16)."""
     dev = _check_dev(idx, w, b, channels, positions, norm.median, norm.b)
     ctx = _lib.context(dev)
-    ii = idx.long().contiguous()
+    ii, c16 = codes_in(idx, cfg, "project_out")
     if ii.shape[-1] != cfg.num_codebooks:
         raise AssertionError("last dim of indices must be num_codebooks")
     dim = w.shape[0]
@@ -582,10 +622,10 @@ def lfq_project_out_inverse_norm(idx: torch.Tensor, w: torch.Tensor, b: Optional
         if tuple(t.shape) != tshape or not t.is_contiguous() or t.dtype != torch.float32:
             raise AssertionError(f"PatchNorm tables must be contiguous fp32 {tshape}, got {tuple(t.shape)}")
     out = torch.empty((*ii.shape[:-1], dim), dtype=torch.float32, device=dev)
-    rc = ctx.lib.dctae_lfq_project_out_inverse_norm(ctx.h, C.byref(cfg), ptr(ii), n, dim, ptr(w), ptr(b),
-                                                    C.byref(norm.c()), p.max_patch_h, p.max_patch_w, ptr(ch),
-                                                    ptr(pos), ptr(out), _lib.stream_ptr(dev))
-    ctx.check(rc, "dctae_lfq_project_out_inverse_norm")
+    name = "dctae_lfq_project_out_inverse_norm" + c16
+    rc = getattr(ctx.lib, name)(ctx.h, C.byref(cfg), ptr(ii), n, dim, ptr(w), ptr(b), C.byref(norm.c()),
+                                p.max_patch_h, p.max_patch_w, ptr(ch), ptr(pos), ptr(out), _lib.stream_ptr(dev))
+    ctx.check(rc, name)
     return out
 
 
@@ -698,8 +738,14 @@ def _decode_call(ctx, cfg: FECfg, table: DecodeTable, ids, key_pad, pos, ch, nor
     dctae_decode_normed of the packed batch into the flat buffer ``out``; the
     tensors as the library reads them (int64 / bool / fp32, contiguous).
     out_dtype=torch.uint8: the byte-output twin of either (dctae_decode_u8 /
-    dctae_decode_normed_u8), ``out`` a uint8 buffer in the same layout."""
+    dctae_decode_normed_u8), ``out`` a uint8 buffer in the same layout.
+    codes: int64, or int16 read as they are (dctae_decode_c16 / dctae_decode_u8_c16);
+    any other dtype is a TypeError."""
     name = ("dctae_decode_normed" if normed else "dctae_decode") + out_dtype_suffix(out_dtype, "decode out_dtype")
+    if codes is not None and not normed:
+        name += codes_dtype_suffix(codes.dtype, "decode codes")
+        if codes.dtype == torch.int16 and lfq is not None:
+            check_codes16(lfq, "decode")
     if out.dtype != out_dtype:
         raise TypeError(f"{name}: the output buffer is {out.dtype}")
     batch = (ctx.h, C.byref(cfg), table.R, *table.c_args(), ptr(ids), ptr(key_pad), ptr(pos), ptr(ch))
@@ -774,7 +820,7 @@ def decode(p: FEParams, ids: torch.Tensor, key_pad: torch.Tensor, positions: tor
         table = decode_table(p, ids, key_pad, positions, channels, patch_sizes, original_sizes)
     out_dtype_suffix(out_dtype, "decode out_dtype")
     out = torch.empty(table.total, dtype=out_dtype, device=dev)
-    cc = codes.long().contiguous() if codes is not None else None
+    cc = codes_in(codes, lfq, "decode")[0] if codes is not None else None   # int16 codes: no widened copy
     pp = patches.float().contiguous() if patches is not None else None
     if normed and (norm is None or codes is not None):
         raise AssertionError("normed decode needs the PatchNorm state and patches (no codes)")

@@ -3,6 +3,7 @@
 // operators of dctae_model.hip and the fused optimizer step of dctae_optim.hip.
 #include "dctae_ctx.h"
 #include "dctae_model.h"
+#include "../../include/dctae_codes16.h"
 
 using namespace dctae;
 
@@ -343,57 +344,101 @@ static int lfq_proj_check(dctae_ctx* ctx, const dctae_lfq* lfq, int64_t n, int32
   return 0;
 }
 
+// idx / ct: the caller's indices and their type (int16: dctae_codes16.h)
 static int lfq_project_in_impl(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x, int64_t n, int32_t dim,
-                               const float* w, const float* b, float x_bound, int64_t* idx, void* stream) {
+                               const float* w, const float* b, float x_bound, void* idx, CodeType ct, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
   if (int rc = lfq_proj_check(ctx, lfq, n, dim, x, w, idx, 64)) return rc;
+  if (ct == CodeType::kI16) {
+    if (int rc = check_codes16(ctx, lfq)) return rc;
+    if ((uintptr_t)idx & 1) return fail(ctx, DCTAE_EINVAL, "int16 indices must be 2-byte aligned");
+  }
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   OrderedCall oc(ctx, s);
   uint16_t* wsp;   // the pre-split weight
   if (int rc = oc.scratch(kProj, lfq_proj_scratch_bytes(lfq->codebook_dim * lfq->num_codebooks, dim), &wsp)) return rc;
   Timer t(ctx, s, "lfq_project_in");
-  launch_lfq_project_in(x, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, idx, wsp, s,
-                        ctx->opt.gemm_h2 ? x_bound : 0.0f, ctx->opt.lfq_ws != 0);
+  const float xb = ctx->opt.gemm_h2 ? x_bound : 0.0f;
+  if (ct == CodeType::kI16)
+    launch_lfq_project_in_c16(x, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale,
+                              static_cast<int16_t*>(idx), wsp, s, xb, ctx->opt.lfq_ws != 0);
+  else
+    launch_lfq_project_in(x, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale,
+                          static_cast<int64_t*>(idx), wsp, s, xb, ctx->opt.lfq_ws != 0);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 
 int dctae_lfq_project_in(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x, int64_t n, int32_t dim,
                          const float* w, const float* b, int64_t* idx, void* stream) {
-  return lfq_project_in_impl(ctx, lfq, x, n, dim, w, b, 0.0f, idx, stream);
+  return lfq_project_in_impl(ctx, lfq, x, n, dim, w, b, 0.0f, idx, CodeType::kI64, stream);
+}
+
+int dctae_lfq_project_in_c16(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x, int64_t n, int32_t dim,
+                             const float* w, const float* b, int16_t* idx, void* stream) {
+  return lfq_project_in_impl(ctx, lfq, x, n, dim, w, b, 0.0f, idx, CodeType::kI16, stream);
 }
 
 int dctae_lfq_project_in_bounded(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x, int64_t n, int32_t dim,
                                  const float* w, const float* b, float x_bound, int64_t* idx, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
   if (!(x_bound > 0.0f) || !std::isfinite(x_bound)) return fail(ctx, DCTAE_EINVAL, "x_bound must be finite and > 0");
-  return lfq_project_in_impl(ctx, lfq, x, n, dim, w, b, x_bound, idx, stream);
+  return lfq_project_in_impl(ctx, lfq, x, n, dim, w, b, x_bound, idx, CodeType::kI64, stream);
 }
 
-int dctae_lfq_project_out(dctae_ctx* ctx, const dctae_lfq* lfq, const int64_t* idx, int64_t n, int32_t dim,
-                          const float* w, const float* b, float* out, void* stream) {
+// the checks project_out's two forms share; int16 indices (dctae_codes16.h) are
+// loaded one by one, so they need 2-byte alignment where int64 ones need 16
+static int lfq_project_out_check(dctae_ctx* ctx, const dctae_lfq* lfq, const CodeSrc& idx, int64_t n, int32_t dim,
+                                 const float* w, const float* out) {
+  const bool c16 = idx.type == CodeType::kI16;
+  if (int rc = lfq_proj_check(ctx, lfq, n, dim, c16 ? (const void*)w : idx.p, w, out, 32, true)) return rc;
+  if (!c16) return 0;
+  if (n > 0 && !idx.p) return fail(ctx, DCTAE_EINVAL, "bad LFQ projection tensors");
+  if ((uintptr_t)idx.p & 1) return fail(ctx, DCTAE_EINVAL, "int16 indices must be 2-byte aligned");
+  return check_codes16(ctx, lfq);
+}
+
+static int lfq_project_out_impl(dctae_ctx* ctx, const dctae_lfq* lfq, const CodeSrc& idx, int64_t n, int32_t dim,
+                                const float* w, const float* b, float* out, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
-  if (int rc = lfq_proj_check(ctx, lfq, n, dim, idx, w, out, 32, true)) return rc;
+  if (int rc = lfq_project_out_check(ctx, lfq, idx, n, dim, w, out)) return rc;
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   OrderedCall oc(ctx, s);
   uint16_t* wsp;
   if (int rc = oc.scratch(kProj, lfq_proj_scratch_bytes(dim, lfq->codebook_dim * lfq->num_codebooks), &wsp)) return rc;
   Timer t(ctx, s, "lfq_project_out");
-  launch_lfq_project_out(idx, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out, wsp, s,
+  launch_lfq_project_out(idx.p, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out, wsp, s,
                          nullptr, nullptr, nullptr, nullptr, 0.f, 0, 0, nullptr, ctx->opt.gemm_h2 != 0,
-                         ctx->opt.lfq_ws != 0);
+                         ctx->opt.lfq_ws != 0, idx.type);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 
-int dctae_lfq_project_out_inverse_norm(dctae_ctx* ctx, const dctae_lfq* lfq, const int64_t* idx, int64_t n,
-                                       int32_t dim, const float* w, const float* b, const dctae_norm* norm,
-                                       int32_t max_patch_h, int32_t max_patch_w, const int64_t* channels,
-                                       const int64_t* positions, float* out, void* stream) {
+int dctae_lfq_project_out(dctae_ctx* ctx, const dctae_lfq* lfq, const int64_t* idx, int64_t n, int32_t dim,
+                          const float* w, const float* b, float* out, void* stream) {
+  return lfq_project_out_impl(ctx, lfq, idx, n, dim, w, b, out, stream);
+}
+
+int dctae_lfq_project_in_bounded_c16(dctae_ctx* ctx, const dctae_lfq* lfq, const float* x, int64_t n, int32_t dim,
+                                     const float* w, const float* b, float x_bound, int16_t* idx, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
-  if (int rc = lfq_proj_check(ctx, lfq, n, dim, idx, w, out, 32, true)) return rc;
+  if (!(x_bound > 0.0f) || !std::isfinite(x_bound)) return fail(ctx, DCTAE_EINVAL, "x_bound must be finite and > 0");
+  return lfq_project_in_impl(ctx, lfq, x, n, dim, w, b, x_bound, idx, CodeType::kI16, stream);
+}
+
+int dctae_lfq_project_out_c16(dctae_ctx* ctx, const dctae_lfq* lfq, const int16_t* idx, int64_t n, int32_t dim,
+                              const float* w, const float* b, float* out, void* stream) {
+  return lfq_project_out_impl(ctx, lfq, idx, n, dim, w, b, out, stream);
+}
+
+static int lfq_project_out_inverse_norm_impl(dctae_ctx* ctx, const dctae_lfq* lfq, const CodeSrc& idx, int64_t n,
+                                             int32_t dim, const float* w, const float* b, const dctae_norm* norm,
+                                             int32_t max_patch_h, int32_t max_patch_w, const int64_t* channels,
+                                             const int64_t* positions, float* out, void* stream) {
+  if (!ctx) return DCTAE_EINVAL;
+  if (int rc = lfq_project_out_check(ctx, lfq, idx, n, dim, w, out)) return rc;
   if (!norm || !norm->median_dev || !norm->b_dev || max_patch_h < 1 || max_patch_w < 1 ||
       (n > 0 && (!channels || !positions)))
     return fail(ctx, DCTAE_EINVAL, "inverse PatchNorm needs tables, max_patch_h/w and channels / positions");
@@ -407,11 +452,27 @@ int dctae_lfq_project_out_inverse_norm(dctae_ctx* ctx, const dctae_lfq* lfq, con
   uint16_t* wsp;
   if (int rc = oc.scratch(kProj, lfq_proj_scratch_bytes(dim, lfq->codebook_dim * lfq->num_codebooks), &wsp)) return rc;
   Timer t(ctx, s, "lfq_project_out");
-  launch_lfq_project_out(idx, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out, wsp, s,
+  launch_lfq_project_out(idx.p, n, dim, w, b, lfq->codebook_dim, lfq->num_codebooks, lfq->codebook_scale, out, wsp, s,
                          channels, positions, norm->median_dev, norm->b_dev, norm->eps, max_patch_h, max_patch_w,
-                         ctx->err_dev, ctx->opt.gemm_h2 != 0, ctx->opt.lfq_ws != 0);
+                         ctx->err_dev, ctx->opt.gemm_h2 != 0, ctx->opt.lfq_ws != 0, idx.type);
   HIPCHK(ctx, hipGetLastError());
   return 0;
+}
+
+int dctae_lfq_project_out_inverse_norm(dctae_ctx* ctx, const dctae_lfq* lfq, const int64_t* idx, int64_t n,
+                                       int32_t dim, const float* w, const float* b, const dctae_norm* norm,
+                                       int32_t max_patch_h, int32_t max_patch_w, const int64_t* channels,
+                                       const int64_t* positions, float* out, void* stream) {
+  return lfq_project_out_inverse_norm_impl(ctx, lfq, idx, n, dim, w, b, norm, max_patch_h, max_patch_w, channels,
+                                           positions, out, stream);
+}
+
+int dctae_lfq_project_out_inverse_norm_c16(dctae_ctx* ctx, const dctae_lfq* lfq, const int16_t* idx, int64_t n,
+                                           int32_t dim, const float* w, const float* b, const dctae_norm* norm,
+                                           int32_t max_patch_h, int32_t max_patch_w, const int64_t* channels,
+                                           const int64_t* positions, float* out, void* stream) {
+  return lfq_project_out_inverse_norm_impl(ctx, lfq, idx, n, dim, w, b, norm, max_patch_h, max_patch_w, channels,
+                                           positions, out, stream);
 }
 
 // ---- VectorQuantize inference (dctae_vq.hip) --------------------------------

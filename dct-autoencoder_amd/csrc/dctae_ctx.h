@@ -279,8 +279,19 @@ int decode_check(dctae_ctx* ctx, const DecodeBatch& B, const char* own, bool img
 int decode_geometry(dctae_ctx* ctx, const DecodeBatch& B, std::vector<ImgDesc>& D, int64_t* max_hw);
 int decode_gemm_pair(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImgDesc& d, float* ws, GemmProblem* g1,
                      GemmProblem* g2, const float** CW, const float** CH);
+// the caller's codes with their type as a tag (int64 from dctae.h, int16 from dctae_codes16.h)
+struct CodeSrc {
+  const void* p = nullptr;
+  CodeType type = CodeType::kI64;
+  CodeSrc() = default;
+  CodeSrc(const int64_t* c) : p(c) {}
+  CodeSrc(const int16_t* c) : p(c), type(CodeType::kI16) {}
+  explicit operator bool() const { return p != nullptr; }
+};
+// int16 codes hold codebook_dim <= 15 bits (dctae_codes16.h); 0, or the refusal
+int check_codes16(dctae_ctx* ctx, const dctae_lfq* lfq);
 DecodeArgs decode_args(const dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* norm, const dctae_lfq* lfq,
-                       const int64_t* codes, const float* patches, const int32_t* lut, bool normed);
+                       const void* codes, const float* patches, const int32_t* lut, bool normed);
 
 // ---- dctae_encode.hip ----
 void drop_encode_plan(dctae_ctx* ctx);   // dctae_ctx_destroy: EncPlan is complete only there

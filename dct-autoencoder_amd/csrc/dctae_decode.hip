@@ -1,7 +1,9 @@
 // The decode engine: dctae_decode and dctae_decode_normed, and their byte-output
-// forms dctae_decode_u8 and dctae_decode_normed_u8 (include/dctae_u8_out.h).
+// forms dctae_decode_u8 and dctae_decode_normed_u8 (include/dctae_u8_out.h), and
+// the int16-code forms dctae_decode_c16 and dctae_decode_u8_c16 (include/dctae_codes16.h).
 #include "dctae_ctx.h"
 #include "../../include/dctae_u8_out.h"
+#include "../../include/dctae_codes16.h"
 
 using namespace dctae;
 
@@ -75,7 +77,7 @@ int decode_gemm_pair(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImgDesc& d, 
 // B.img_lut; normed: `patches` are PatchNorm outputs that the kernel inverts
 // (the FFT path's column kernel)
 DecodeArgs decode_args(const dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* norm, const dctae_lfq* lfq,
-                       const int64_t* codes, const float* patches, const int32_t* lut, bool normed) {
+                       const void* codes, const float* patches, const int32_t* lut, bool normed) {
   DecodeArgs a{};
   a.ids = B.ids;
   a.key_pad = B.key_pad;
@@ -104,13 +106,20 @@ DecodeArgs decode_args(const dctae_ctx* ctx, const DecodeBatch& B, const dctae_n
   return a;
 }
 
+int check_codes16(dctae_ctx* ctx, const dctae_lfq* lfq) {
+  if (lfq && lfq->codebook_dim > 15)
+    return fail(ctx, DCTAE_EINVAL, "int16 codes hold codebook_dim <= 15 bits, got codebook_dim = " +
+                                       std::to_string(lfq->codebook_dim));
+  return 0;
+}
+
 }  // namespace dctae
 
 // decode of 512 x 512 images on the FFT path: token map -> column DCT-III
 // (tokens expanded in the kernel) -> U -> row DCT-III + IPT -> RGB.
 // rgb / px: the caller's images and their pixel type (ImgDesc::rgb_off in pixels)
 static int decode_fft(OrderedCall& oc, const DecodeBatch& B, std::vector<ImgDesc>& D, const FftPlan& fpl,
-                      const dctae_norm* norm, const dctae_lfq* lfq, const int64_t* codes, const float* patches,
+                      const dctae_norm* norm, const dctae_lfq* lfq, const CodeSrc& codes, const float* patches,
                       void* rgb, PixelType px, bool normed) {
   dctae_ctx* ctx = oc.ctx;
   const hipStream_t s = oc.s;
@@ -148,7 +157,7 @@ static int decode_fft(OrderedCall& oc, const DecodeBatch& B, std::vector<ImgDesc
   const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
   int32_t* map = (int32_t*)(ws + map_off);
   HIPCHK(ctx, hipMemsetAsync(map, 0xFF, (size_t)map_n * 4, s));
-  const DecodeArgs a = decode_args(ctx, B, norm, lfq, codes, patches, (const int32_t*)(pd + lut_off), normed);
+  const DecodeArgs a = decode_args(ctx, B, norm, lfq, codes.p, patches, (const int32_t*)(pd + lut_off), normed);
   const float2* tw = ctx->fft_tab + fpl.tw_off;
   const float4* pre = reinterpret_cast<const float4*>(ctx->fft_tab + fpl.ipre_off);
   {
@@ -158,9 +167,9 @@ static int decode_fft(OrderedCall& oc, const DecodeBatch& B, std::vector<ImgDesc
   {
     Timer t(ctx, s, "idct_cols");
     if (band)
-      launch_idct_cols512b(dd, n_img, ws, map, tw, pre, a, s);
+      launch_idct_cols512b(dd, n_img, ws, map, tw, pre, a, s, codes.type);
     else
-      launch_idct_cols512(dd, n_img, D[0].qw, ws, map, tw, pre, a, s);
+      launch_idct_cols512(dd, n_img, D[0].qw, ws, map, tw, pre, a, s, codes.type);
   }
   {
     Timer t(ctx, s, "idct_rows");
@@ -178,9 +187,11 @@ static int decode_fft(OrderedCall& oc, const DecodeBatch& B, std::vector<ImgDesc
 // are image-independent), other geometries run dctae_norm_inverse's kernel
 // into the staging buffer first.  px: the pixel type of the caller's images
 // (B.out_off in pixels); the tag rides to the kernels that write them, every
-// workspace request, plan entry and launch before them is the same
+// workspace request, plan entry and launch before them is the same.  codes:
+// the caller's codes with their type, a tag that rides to the kernels that
+// load them (the column kernels of the FFT path, k_scatter_tokens) in the same way
 static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* norm, const dctae_lfq* lfq,
-                       const int64_t* codes, const float* patches, void* rgb, PixelType px, bool normed) {
+                       const CodeSrc& codes, const float* patches, void* rgb, PixelType px, bool normed) {
   hipSetDevice(ctx->device);
   const dctae_fe_cfg* cfg = B.cfg;
   const hipStream_t s = B.s;
@@ -194,6 +205,7 @@ static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* n
   if (codes) {
     if (!norm || !norm->median_dev || !norm->b_dev) return fail(ctx, DCTAE_EINVAL, "decode from codes needs PatchNorm");
     if ((rc = check_lfq(ctx, lfq, PP))) return rc;
+    if (codes.type == CodeType::kI16 && (rc = check_codes16(ctx, lfq))) return rc;
   } else if (n_rows > 0 && !patches) {
     return fail(ctx, DCTAE_EINVAL, "decode needs codes or patches");
   }
@@ -260,7 +272,7 @@ static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* n
   const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
   HIPCHK(ctx, hipMemsetAsync(ws, 0, (size_t)wsf * 4, s));
   // PatchNorm-space patches were inverted into the staging buffer above: plain patches here
-  const DecodeArgs a = decode_args(ctx, B, norm, lfq, codes, patches, (const int32_t*)(pd + lut_off), false);
+  const DecodeArgs a = decode_args(ctx, B, norm, lfq, codes.p, patches, (const int32_t*)(pd + lut_off), false);
   int32_t* gmap = (int32_t*)(ws + gmap_off);
   HIPCHK(ctx, hipMemsetAsync(gmap, 0xFF, (size_t)gmap_n * 4, s));
   {
@@ -269,7 +281,7 @@ static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* n
   }
   {
     Timer t(ctx, s, "scatter_tokens");
-    launch_scatter_tokens((int64_t)n_rows * S, dd, ws, a, gmap, s);
+    launch_scatter_tokens((int64_t)n_rows * S, dd, ws, a, gmap, s, codes.type);
   }
   {
     Timer t(ctx, s, "idct_cols");
@@ -320,7 +332,7 @@ int dctae_decode_normed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows,
                       (hipStream_t)stream};
   if (!ctx) return DCTAE_EINVAL;
   if (n_rows > 0 && !normed_patches) return fail(ctx, DCTAE_EINVAL, "decode needs the PatchNorm-space patches");
-  return decode_impl(ctx, B, norm, nullptr, nullptr, normed_patches, rgb, PixelType::kF32, true);
+  return decode_impl(ctx, B, norm, nullptr, CodeSrc(), normed_patches, rgb, PixelType::kF32, true);
 }
 
 int dctae_decode_normed_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut,
@@ -332,7 +344,30 @@ int dctae_decode_normed_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_ro
                       (hipStream_t)stream};
   if (!ctx) return DCTAE_EINVAL;
   if (n_rows > 0 && !normed_patches) return fail(ctx, DCTAE_EINVAL, "decode needs the PatchNorm-space patches");
-  return decode_impl(ctx, B, norm, nullptr, nullptr, normed_patches, rgb, PixelType::kU8, true);
+  return decode_impl(ctx, B, norm, nullptr, CodeSrc(), normed_patches, rgb, PixelType::kU8, true);
+}
+
+// the int16-code entries (include/dctae_codes16.h): the same calls, the code type apart
+int dctae_decode_c16(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut, int32_t lut_w,
+                     int32_t n_img, const int32_t* out_hw, const int64_t* out_off, const int32_t* patch_hw,
+                     const int64_t* ids, const uint8_t* key_pad, const int64_t* pos, const int64_t* ch,
+                     const dctae_norm* norm, const dctae_lfq* lfq, const int16_t* codes, const float* patches,
+                     float* rgb, void* stream) {
+  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
+                      (hipStream_t)stream};
+  if (!ctx) return DCTAE_EINVAL;
+  return decode_impl(ctx, B, norm, lfq, codes, patches, rgb, PixelType::kF32, false);
+}
+
+int dctae_decode_u8_c16(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut,
+                        int32_t lut_w, int32_t n_img, const int32_t* out_hw, const int64_t* out_off,
+                        const int32_t* patch_hw, const int64_t* ids, const uint8_t* key_pad, const int64_t* pos,
+                        const int64_t* ch, const dctae_norm* norm, const dctae_lfq* lfq, const int16_t* codes,
+                        const float* patches, uint8_t* rgb, void* stream) {
+  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
+                      (hipStream_t)stream};
+  if (!ctx) return DCTAE_EINVAL;
+  return decode_impl(ctx, B, norm, lfq, codes, patches, rgb, PixelType::kU8, false);
 }
 
 }  // extern "C"

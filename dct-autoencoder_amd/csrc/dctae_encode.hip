@@ -3,6 +3,7 @@
 #include "dctae_ctx.h"
 #include "dctae_enc_layout.h"
 #include "../../include/dctae_u8.h"
+#include "../../include/dctae_codes16.h"
 
 using namespace dctae;
 
@@ -72,6 +73,27 @@ struct ImageSet {
   }
 };
 
+// The packed outputs of a call: dctae_packed_out or dctae_packed_out16, with
+// the code type as a tag.  ok = false: the caller's pointer was NULL.
+struct PackedOut {
+  bool ok = false;
+  void* codes_dev = nullptr;
+  int64_t *positions_dev = nullptr, *channels_dev = nullptr, *image_ids_dev = nullptr;
+  uint8_t* key_pad_dev = nullptr;
+  float *patches_dev = nullptr, *raw_patches_dev = nullptr, *scores_dev = nullptr;
+  CodeType ct = CodeType::kI64;
+  PackedOut() = default;
+  template <typename T>
+  void take(const T* o) {
+    if (!o) return;
+    ok = true, codes_dev = o->codes_dev, positions_dev = o->positions_dev, channels_dev = o->channels_dev;
+    image_ids_dev = o->image_ids_dev, key_pad_dev = o->key_pad_dev, patches_dev = o->patches_dev;
+    raw_patches_dev = o->raw_patches_dev, scores_dev = o->scores_dev;
+  }
+  explicit PackedOut(const dctae_packed_out* o) { take(o); }
+  explicit PackedOut(const dctae_packed_out16* o) : ct(CodeType::kI16) { take(o); }
+};
+
 // One encode call: its arguments and what they ask for.
 struct EncCall {
   const dctae_fe_cfg* cfg;
@@ -79,7 +101,7 @@ struct EncCall {
   const dctae_packing* pack;   // NULL: token mode
   const dctae_norm* norm;
   const dctae_lfq* lfq;
-  const dctae_packed_out* out;
+  PackedOut out;
   const int64_t* tok_off_user;   // token mode: the caller's token offsets
   float *tokens_dev, *scores_dev;
   const float *proj_w, *proj_b;   // fused LFQ projections (dctae_encode_lfq_proj)
@@ -98,12 +120,20 @@ int EncCall::check(dctae_ctx* ctx) {
   full = (pack != nullptr);
   const int n = imgs.n_img;
   const int P = cfg->patch_size, PP = P * P;
-  want_codes = full && out && out->codes_dev;
+  want_codes = full && out.ok && out.codes_dev;
   if (full) {
-    if (!out || !out->positions_dev || !out->channels_dev || !out->image_ids_dev || !out->key_pad_dev)
+    if (!out.ok || !out.positions_dev || !out.channels_dev || !out.image_ids_dev || !out.key_pad_dev)
       return fail(ctx, DCTAE_EINVAL, "packed outputs positions/channels/image_ids/key_pad are required");
-    if ((want_codes || out->patches_dev) && !norm) return fail(ctx, DCTAE_EINVAL, "codes/patches need PatchNorm tables");
+    if ((want_codes || out.patches_dev) && !norm) return fail(ctx, DCTAE_EINVAL, "codes/patches need PatchNorm tables");
     if (want_codes && !proj_w && (rc = check_lfq(ctx, lfq, PP))) return rc;
+    if (want_codes && out.ct == CodeType::kI16) {   // dctae_codes16.h: the limit and the alignment rule
+      if ((rc = check_codes16(ctx, lfq))) return rc;
+      // k_sort_pack2's ncb == 14 branch stores two codes (4 bytes) at once; every other store is one code
+      const uintptr_t al = lfq && lfq->num_codebooks == 14 ? 4 : 2;
+      if ((uintptr_t)out.codes_dev % al)
+        return fail(ctx, DCTAE_EINVAL, "int16 codes_dev must be " + std::to_string(al) + "-byte aligned" +
+                                           (al == 4 ? " at num_codebooks = 14 (two codes per store)" : ""));
+    }
     if (proj_w && (!want_codes || !lfq || lfq->codebook_dim < 1 || lfq->codebook_dim > 16 ||
                    lfq->num_codebooks < 1 || lfq->num_codebooks > 64 || PP % 4 != 0 ||
                    lfq->codebook_dim * lfq->num_codebooks > 256 || ((uintptr_t)proj_w & 15)))
@@ -115,11 +145,11 @@ int EncCall::check(dctae_ctx* ctx) {
   }
   if (norm && (!norm->median_dev || !norm->b_dev)) return fail(ctx, DCTAE_EINVAL, "PatchNorm tables are NULL");
   ncb = want_codes ? lfq->num_codebooks : 0;
-  want_raw = (full && out->raw_patches_dev) || (!full && tokens_dev);
+  want_raw = (full && out.raw_patches_dev) || (!full && tokens_dev);
   // LFQ with projections: the column epilogues stage the PatchNorm output,
   // dctae_lfq_project_in turns the staged tokens into staged u16 codes, and the
   // sort / pack gathers those as usual
-  want_norm = full && (out->patches_dev || proj_w);
+  want_norm = full && (out.patches_dev || proj_w);
   return 0;
 }
 
@@ -479,9 +509,9 @@ void dctae::drop_encode_plan(dctae_ctx* ctx) {
   ctx->enc_plan = nullptr;
 }
 
-static PackSinks pack_sinks(const dctae_packed_out* out) {
-  return PackSinks{out->codes_dev,   out->positions_dev,   out->channels_dev, out->image_ids_dev,
-                   out->patches_dev, out->raw_patches_dev, out->scores_dev,   out->key_pad_dev};
+static PackSinks pack_sinks(const PackedOut& out) {
+  return PackSinks{out.codes_dev,   out.positions_dev,   out.channels_dev, out.image_ids_dev,
+                   out.patches_dev, out.raw_patches_dev, out.scores_dev,   out.key_pad_dev};
 }
 
 // token staging for the whole call (flat token order, global offsets)
@@ -548,6 +578,7 @@ struct EncLaunch {
   TokenSinks sk, skc;        // the call's staging; the column kernels' sinks
   EncParams eps;             // the pack's parameters
   PackSinks ps;
+  CodeType ct;               // the type behind ps.codes
 
   void gemm(const ChunkJob& j, const PlanList<TileRef>& tiles, hipStream_t st, int share) const {
     if (j.h2)
@@ -655,7 +686,7 @@ struct EncLaunch {
 
   // sort / pack of images [a, a + m) on a stream
   void sort_pack(int a, int m, hipStream_t st) const {
-    launch_sort_pack(all_d + a, m, next_pow2(E.max_T), eps, sk, ps, st, ctx->opt.sort_kernel, E.max_T);
+    launch_sort_pack(all_d + a, m, next_pow2(E.max_T), eps, sk, ps, st, ctx->opt.sort_kernel, E.max_T, ct);
   }
 
   // halves (option): see Options::halves.  The plan kernel variant (>= 2) of
@@ -775,11 +806,12 @@ static int encode_call(dctae_ctx* ctx, EncCall& c, hipStream_t s) {
   }
   if (full) {
     L.ps = pack_sinks(c.out);
+    L.ct = c.out.ct;
     // rows filled to max_seq_len (e.g. one 512^2 image per row) have no pads:
     // the sort kernel writes their key_pad zeros, no k_pad_fill launch
     if (c.pack->n_rows > 0 && E.any_pad) {
       Timer t(ctx, s, "pad_fill");
-      launch_pad_fill(E.rowlen.at(pd), c.pack->n_rows, ep, c.out->key_pad_dev, L.ps, s);
+      launch_pad_fill(E.rowlen.at(pd), c.pack->n_rows, ep, c.out.key_pad_dev, L.ps, s, L.ct);
     }
   }
   if ((rc = token_sinks(oc, c, E, L.sk))) return rc;
@@ -833,9 +865,10 @@ static int encode_call(dctae_ctx* ctx, EncCall& c, hipStream_t s) {
   return 0;
 }
 
-// the three encode entries for either image descriptor (the pixel type rides in the ImageSet)
+// the three encode entries for either image descriptor and either code type
+// (the pixel type rides in the ImageSet, the code type in the PackedOut)
 static int encode_packed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImageSet& imgs, const dctae_packing* pack,
-                         const dctae_norm* norm, const dctae_lfq* lfq, const dctae_packed_out* out, void* stream) {
+                         const dctae_norm* norm, const dctae_lfq* lfq, const PackedOut& out, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
   if (!pack) return fail(ctx, DCTAE_EINVAL, "packing descriptor is NULL");
   hipSetDevice(ctx->device);
@@ -846,10 +879,10 @@ static int encode_packed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImageSet
 
 static int encode_packed_proj(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImageSet& imgs, const dctae_packing* pack,
                               const dctae_norm* norm, const dctae_lfq* lfq, const float* w_in_dev,
-                              const float* b_in_dev, const dctae_packed_out* out, void* stream) {
+                              const float* b_in_dev, const PackedOut& out, void* stream) {
   if (!ctx) return DCTAE_EINVAL;
   if (!pack) return fail(ctx, DCTAE_EINVAL, "packing descriptor is NULL");
-  if (!w_in_dev || !out || !out->codes_dev) return fail(ctx, DCTAE_EINVAL, "project_in weight and codes output required");
+  if (!w_in_dev || !out.ok || !out.codes_dev) return fail(ctx, DCTAE_EINVAL, "project_in weight and codes output required");
   hipSetDevice(ctx->device);
   EncCall c{};
   c.cfg = cfg, c.imgs = imgs, c.pack = pack, c.norm = norm, c.lfq = lfq, c.out = out;
@@ -871,13 +904,13 @@ extern "C" {
 
 int dctae_encode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const dctae_packing* pack,
                  const dctae_norm* norm, const dctae_lfq* lfq, const dctae_packed_out* out, void* stream) {
-  return encode_packed(ctx, cfg, ImageSet(imgs), pack, norm, lfq, out, stream);
+  return encode_packed(ctx, cfg, ImageSet(imgs), pack, norm, lfq, PackedOut(out), stream);
 }
 
 int dctae_encode_lfq_proj(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
                           const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
                           const float* w_in_dev, const float* b_in_dev, const dctae_packed_out* out, void* stream) {
-  return encode_packed_proj(ctx, cfg, ImageSet(imgs), pack, norm, lfq, w_in_dev, b_in_dev, out, stream);
+  return encode_packed_proj(ctx, cfg, ImageSet(imgs), pack, norm, lfq, w_in_dev, b_in_dev, PackedOut(out), stream);
 }
 
 int dctae_spectrum_tokens(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const int64_t* tok_off,
@@ -888,18 +921,44 @@ int dctae_spectrum_tokens(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_i
 // the byte-image entries (include/dctae_u8.h): the same calls, the pixel type apart
 int dctae_encode_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images_u8* imgs, const dctae_packing* pack,
                     const dctae_norm* norm, const dctae_lfq* lfq, const dctae_packed_out* out, void* stream) {
-  return encode_packed(ctx, cfg, ImageSet(imgs), pack, norm, lfq, out, stream);
+  return encode_packed(ctx, cfg, ImageSet(imgs), pack, norm, lfq, PackedOut(out), stream);
 }
 
 int dctae_encode_lfq_proj_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images_u8* imgs,
                              const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
                              const float* w_in_dev, const float* b_in_dev, const dctae_packed_out* out, void* stream) {
-  return encode_packed_proj(ctx, cfg, ImageSet(imgs), pack, norm, lfq, w_in_dev, b_in_dev, out, stream);
+  return encode_packed_proj(ctx, cfg, ImageSet(imgs), pack, norm, lfq, w_in_dev, b_in_dev, PackedOut(out), stream);
 }
 
 int dctae_spectrum_tokens_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images_u8* imgs,
                              const int64_t* tok_off, float* tokens_dev, float* scores_dev, void* stream) {
   return encode_tokens(ctx, cfg, ImageSet(imgs), tok_off, tokens_dev, scores_dev, stream);
+}
+
+// the int16-code entries (include/dctae_codes16.h): the same calls, the code type apart
+int dctae_encode_c16(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs, const dctae_packing* pack,
+                     const dctae_norm* norm, const dctae_lfq* lfq, const dctae_packed_out16* out, void* stream) {
+  return encode_packed(ctx, cfg, ImageSet(imgs), pack, norm, lfq, PackedOut(out), stream);
+}
+
+int dctae_encode_u8_c16(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images_u8* imgs,
+                        const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
+                        const dctae_packed_out16* out, void* stream) {
+  return encode_packed(ctx, cfg, ImageSet(imgs), pack, norm, lfq, PackedOut(out), stream);
+}
+
+int dctae_encode_lfq_proj_c16(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images* imgs,
+                              const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
+                              const float* w_in_dev, const float* b_in_dev, const dctae_packed_out16* out,
+                              void* stream) {
+  return encode_packed_proj(ctx, cfg, ImageSet(imgs), pack, norm, lfq, w_in_dev, b_in_dev, PackedOut(out), stream);
+}
+
+int dctae_encode_lfq_proj_u8_c16(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const dctae_images_u8* imgs,
+                                 const dctae_packing* pack, const dctae_norm* norm, const dctae_lfq* lfq,
+                                 const float* w_in_dev, const float* b_in_dev, const dctae_packed_out16* out,
+                                 void* stream) {
+  return encode_packed_proj(ctx, cfg, ImageSet(imgs), pack, norm, lfq, w_in_dev, b_in_dev, PackedOut(out), stream);
 }
 
 // Full-image orthonormal 2-D DCT (util.py:333-338 on the whole (3, H, W) image)

@@ -152,6 +152,9 @@ __device__ __forceinline__ void icols_map(int img, const ImgDesc& d, int c, int 
   }
 }
 
+// Code: the type of a.codes (CodeType).  An int16 code is one sign-extending
+// 2-byte load at any 2-byte alignment (the bits the expansion reads are its low 14)
+template <typename Code>
 __device__ __forceinline__ void icols_codes(const DecodeArgs& a, IcTok& t) {
   constexpr int KS = 14;
   const int jl = itid() & 15;
@@ -159,7 +162,10 @@ __device__ __forceinline__ void icols_codes(const DecodeArgs& a, IcTok& t) {
 #pragma unroll
   for (int r = 0; r < 2; ++r) {   // unconditional loads; the low word of the int64 code (lfq.py:117 .int())
     const int64_t s0 = t.sl[r] >= 0 ? t.sl[r] : 0;
-    t.code[r] = reinterpret_cast<const int32_t*>(a.codes)[2 * (s0 * a.ncb + (jl < KS ? jl : 0))];
+    if constexpr (sizeof(Code) == 8)
+      t.code[r] = reinterpret_cast<const int32_t*>(a.codes)[2 * (s0 * a.ncb + (jl < KS ? jl : 0))];
+    else
+      t.code[r] = static_cast<const int16_t*>(a.codes)[s0 * a.ncb + (jl < KS ? jl : 0)];
   }
 }
 
@@ -218,12 +224,13 @@ __device__ __forceinline__ void icols_expand(const IcTok& t, const DecodeArgs& a
     for (int e = tid; e < (N - KS * 32) * KS; e += 256) x[KS * 32 * KS + e] = 0.0f;
 }
 
+template <typename Code>
 __device__ __forceinline__ void icols_fill_x(int img, const ImgDesc& d, int c, int strip,
                                              const int32_t* __restrict__ map, const DecodeArgs& a,
                                              const float2 (&vt)[2][14], float* x, bool zero_tail) {
   IcTok t;
   icols_map(img, d, c, strip, map, a, t);
-  icols_codes(a, t);
+  icols_codes<Code>(a, t);
   icols_expand(t, a, vt, x, zero_tail);
 }
 
@@ -257,6 +264,7 @@ __device__ __forceinline__ void icols_vt(int c, int strip, const DecodeArgs& a, 
 // one (image, channel, tile column) of the column pass; vt[r][p] = the
 // (code bit 1, code bit 0) values of this thread's tile row r, element p
 // (inverse PatchNorm of +-scale, image-independent: loaded once per block)
+template <typename Code>
 __device__ __forceinline__ void idct_col_image(int img, const ImgDesc& d, int c, int strip, float* __restrict__ ws,
                                                const int32_t* __restrict__ map, const DecodeArgs& a,
                                                const float2 (&vt)[2][14], IColsLds& L, const float4* pre_s,
@@ -265,7 +273,7 @@ __device__ __forceinline__ void idct_col_image(int img, const ImgDesc& d, int c,
   constexpr int N = 512, M = 256, KS = 14, S16 = 257;
   const int tid = itid();
   // ---- 1. tokens -> X rows 14 h + jl (tile h = g16 + 16 r)
-  icols_fill_x(img, d, c, strip, map, a, vt, L.x, true);
+  icols_fill_x<Code>(img, d, c, strip, map, a, vt, L.x, true);
   __syncthreads();
   // lanes of columns 14 / 15 (tid >= 224) redo column 13: same reads, same
   // values, same stores (no divergent branches)
@@ -347,7 +355,7 @@ __device__ __forceinline__ void idct_col_image(int img, const ImgDesc& d, int c,
 // block = (channel c, tile column strip) item x IPB consecutive images (the
 // image loop unrolled: straight-line register allocation); items dealt so the
 // 8 XCD groups (b % 8) own contiguous runs of tile columns
-template <int IPB>
+template <int IPB, typename Code>
 __global__ __launch_bounds__(256) void k_idct_cols512(const ImgDesc* __restrict__ imgs, int n_img, int n_items, int qw,
                                                       float* __restrict__ ws, const int32_t* __restrict__ map,
                                                       const float2* __restrict__ tw, const float4* __restrict__ pre,
@@ -371,7 +379,7 @@ __global__ __launch_bounds__(256) void k_idct_cols512(const ImgDesc* __restrict_
 #pragma unroll
   for (int u = 0; u < IPB; ++u) {
     const int img = i0 + u;
-    if (img < n_img) idct_col_image(img, imgs[img], c, strip, ws, map, a, vt, L, pre_s, tw_s);
+    if (img < n_img) idct_col_image<Code>(img, imgs[img], c, strip, ws, map, a, vt, L, pre_s, tw_s);
   }
 }
 
@@ -545,7 +553,7 @@ struct ICols512bLds {
   float4 pre[256];                // (conj a_k, conj b_k)
 };                                // 40,960 B: 4 blocks per CU
 
-template <int IPB>
+template <int IPB, typename Code>
 __global__ __launch_bounds__(256) void k_idct_cols512b(const ImgDesc* __restrict__ imgs, int n_img,
                                                        float* __restrict__ ws, const int32_t* __restrict__ map,
                                                        const float2* __restrict__ tw, const float4* __restrict__ pre,
@@ -570,7 +578,7 @@ __global__ __launch_bounds__(256) void k_idct_cols512b(const ImgDesc* __restrict
   // image ahead, issued right after the expansion
   IcTok tk, tm;   // this image's map entries + codes; the next image's map entries
   icols_map(i0, imgs[i0], c, strip, map, a, tk);
-  icols_codes(a, tk);
+  icols_codes<Code>(a, tk);
   if (IPB > 1) {
     const int i1 = min(i0 + 1, n_img - 1);
     icols_map(i1, imgs[i1], c, strip, map, a, tm);
@@ -587,7 +595,7 @@ __global__ __launch_bounds__(256) void k_idct_cols512b(const ImgDesc* __restrict
     // through this image's transform and stores (unconditional: past the end
     // of the list the last image reloads itself)
     IcTok tn = tm;
-    if (u + 1 < IPB) icols_codes(a, tn);
+    if (u + 1 < IPB) icols_codes<Code>(a, tn);
     const int img_n2 = min(img + 2, n_img - 1);
     if (u + 2 < IPB) icols_map(img_n2, imgs[img_n2], c, strip, map, a, tm);
     __syncthreads();
@@ -635,22 +643,29 @@ __global__ __launch_bounds__(256) void k_idct_cols512b(const ImgDesc* __restrict
 }
 
 void launch_idct_cols512b(const ImgDesc* imgs, int n_img, float* ws, const int32_t* map, const float2* tw,
-                          const float4* pre, const DecodeArgs& a, hipStream_t s) {
+                          const float4* pre, const DecodeArgs& a, hipStream_t s, CodeType ct) {
   // images per block (same-box A/Bs, decode 1024 x 512^2: 4 1.98, 6 1.93, 8 1.925 / 1.960, 12 1.910 / 1.945, 16 2.19 ms)
   constexpr int IPB = 12;
   const int grid = 8 * 12 * ((n_img + IPB - 1) / IPB);
-  if (n_img > 0)
-    hipLaunchKernelGGL((k_idct_cols512b<IPB>), dim3(grid), dim3(256), 0, s, imgs, n_img, ws, map, tw, pre, a);
+  if (n_img <= 0) return;
+  if (ct == CodeType::kI16)
+    hipLaunchKernelGGL((k_idct_cols512b<IPB, int16_t>), dim3(grid), dim3(256), 0, s, imgs, n_img, ws, map, tw, pre, a);
+  else
+    hipLaunchKernelGGL((k_idct_cols512b<IPB, int64_t>), dim3(grid), dim3(256), 0, s, imgs, n_img, ws, map, tw, pre, a);
 }
 
 void launch_idct_cols512(const ImgDesc* imgs, int n_img, int qw, float* ws, const int32_t* map, const float2* tw,
-                         const float4* pre, const DecodeArgs& a, hipStream_t s) {
+                         const float4* pre, const DecodeArgs& a, hipStream_t s, CodeType ct) {
   constexpr int IPB = 2;
   const int n_items = 3 * qw, per_x = (n_items + 7) / 8;
   const int grid = 8 * per_x * ((n_img + IPB - 1) / IPB);
-  if (n_img > 0)
-    hipLaunchKernelGGL((k_idct_cols512<IPB>), dim3(grid), dim3(256), 0, s, imgs, n_img, n_items, qw, ws, map, tw,
-                       pre, a);
+  if (n_img <= 0) return;
+  if (ct == CodeType::kI16)
+    hipLaunchKernelGGL((k_idct_cols512<IPB, int16_t>), dim3(grid), dim3(256), 0, s, imgs, n_img, n_items, qw, ws, map,
+                       tw, pre, a);
+  else
+    hipLaunchKernelGGL((k_idct_cols512<IPB, int64_t>), dim3(grid), dim3(256), 0, s, imgs, n_img, n_items, qw, ws, map,
+                       tw, pre, a);
 }
 
 template <typename Out>

@@ -155,8 +155,14 @@ struct TokenSinks {
   float* norm;       // (T, P*P) or null
 };
 
+// The integer type of the caller's LFQ codes (include/dctae_codes16.h): an
+// int16 code c means the int64 code int64(c).  The tag rides from the entry
+// point to the launchers of the kernels that store or load the caller's codes
+// (their template parameter); nothing else of a call depends on it.
+enum class CodeType : int32_t { kI64 = 0, kI16 = 1 };
+
 struct PackSinks {
-  int64_t* codes;     // (R,S,ncb)
+  void* codes;        // (R,S,ncb) of the call's CodeType
   int64_t* pos;       // (R,S,2)
   int64_t* ch;        // (R,S)
   int64_t* ids;       // (R,S)
@@ -171,7 +177,7 @@ struct DecodeArgs {
   const uint8_t* key_pad;   // (R,S)
   const int64_t* pos;       // (R,S,2)
   const int64_t* ch;        // (R,S)
-  const int64_t* codes;     // (R,S,ncb) when use_codes
+  const void* codes;        // (R,S,ncb) of the call's CodeType when use_codes
   const float* patches;     // (R,S,PP) otherwise
   const int32_t* lut;       // (R, lut_w) row-local id -> image index (-1 = none)
   int32_t lut_w, S, P, use_codes;   // use_codes: 1 = codes, 0 = patches, 2 = PatchNorm-space patches (FFT path)

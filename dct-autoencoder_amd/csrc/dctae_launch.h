@@ -54,9 +54,11 @@ void split_matrix_h2(const float* m, int R, int K, std::vector<uint16_t>& out, i
 void launch_tile_epilogue(const ImgDesc* imgs, int n_img, int max_T, const float* ws, const EncParams& ep,
                           const TokenSinks& sk, hipStream_t s, const int2* list = nullptr, int n_list = 0);
 void launch_sort_pack(const ImgDesc* imgs, int n_img, int np2, const EncParams& ep, const TokenSinks& st,
-                      const PackSinks& out, hipStream_t s, int kernel = 1, int max_T = 1 << 30);
+                      const PackSinks& out, hipStream_t s, int kernel = 1, int max_T = 1 << 30,
+                      CodeType ct = CodeType::kI64);
+// ct (here and in the decode's token launchers): the type behind PackSinks::codes / DecodeArgs::codes
 void launch_pad_fill(const int32_t* row_len, int n_rows, const EncParams& ep, uint8_t* key_pad,
-                     const PackSinks& out, hipStream_t s);
+                     const PackSinks& out, hipStream_t s, CodeType ct = CodeType::kI64);
 void launch_norm(const float* x, const int64_t* ch, const int64_t* pos, int64_t n, int PP, int maxph, int maxpw,
                  const float* med, const float* b, float eps, float lo, float hi, int inverse, float* y, int* err,
                  hipStream_t s);
@@ -72,14 +74,19 @@ void launch_lfq_project_in(const float* x, int64_t n, int D, const float* w, con
 void launch_lfq_project_in16(const float* x, int64_t n, int D, const float* w, const float* b, int cd, int ncb,
                              uint16_t* idx, uint16_t* wsp, hipStream_t s,
                              float x_bound = 0.f, bool ws = false);
-void launch_lfq_project_out(const int64_t* idx, int64_t n, int D, const float* w, const float* b, int cd, int ncb,
+// ... into the caller's int16 indices (include/dctae_codes16.h)
+void launch_lfq_project_in_c16(const float* x, int64_t n, int D, const float* w, const float* b, int cd, int ncb,
+                               float scale, int16_t* idx, uint16_t* wsp, hipStream_t s, float x_bound = 0.f,
+                               bool ws = false);
+void launch_lfq_project_out(const void* idx, int64_t n, int D, const float* w, const float* b, int cd, int ncb,
                             float scale, float* out, uint16_t* wsp, hipStream_t s, const int64_t* ch = nullptr,
                             const int64_t* pos = nullptr, const float* med = nullptr, const float* nb = nullptr,
                             float eps = 0.f, int maxph = 0, int maxpw = 0, int* err = nullptr, bool h2 = true,
-                            bool ws = false);
+                            bool ws = false, CodeType ct = CodeType::kI64);
 // dctae_lfq_ws.hip: the W-stationary form of the two (fp16 pieces; 192 < K <= 208, 192 < N <= 224)
 bool lfq_ws_fits(int mode, int K, int N, int cd, int ncb);
-void launch_lfq_ws(int mode, hipStream_t s, const float* x, const int64_t* idx_in, int64_t n, int K, int N,
+// idx_in / ct: mode 1's indices and their type
+void launch_lfq_ws(int mode, hipStream_t s, const float* x, const void* idx_in, CodeType ct, int64_t n, int K, int N,
                    const float* bias, int cd, int ncb, float scale, int64_t* idx_out, float* out, uint16_t* idx16,
                    const int64_t* ch, const int64_t* pos, const float* med, const float* nb, float eps, int maxph,
                    int maxpw, int* err, const uint16_t* wsp, int NPw, int Kp, float a_scale);
@@ -122,7 +129,7 @@ void launch_vq_assign(const float* xp, int64_t nv, int heads, const float* et, c
                       int64_t* ind, hipStream_t s);
 void launch_vq_codes(const int64_t* ind, int64_t nv, const float* embed, int C, float* out, int* err, hipStream_t s);
 void launch_scatter_tokens(int64_t n_tok, const ImgDesc* imgs, float* ws, const DecodeArgs& a, const int32_t* map,
-                           hipStream_t s);
+                           hipStream_t s, CodeType ct = CodeType::kI64);
 
 // PatchNorm training statistics (dctae_stats.hip)
 void launch_stats_lists(const int64_t* ch, const int64_t* pos, const uint8_t* key_pad, int64_t n_tok, int C, int mh,
@@ -157,9 +164,9 @@ void launch_fft_cols_spec(int spec, const ImgDesc* imgs, const int4* blocks, int
 // decode on the FFT path (dctae_idct.hip)
 void launch_dec_map(int64_t n_tok, const ImgDesc* imgs, const DecodeArgs& a, int32_t* map, hipStream_t s);
 void launch_idct_cols512b(const ImgDesc* imgs, int n_img, float* ws, const int32_t* map, const float2* tw,
-                          const float4* pre, const DecodeArgs& a, hipStream_t s);
+                          const float4* pre, const DecodeArgs& a, hipStream_t s, CodeType ct = CodeType::kI64);
 void launch_idct_cols512(const ImgDesc* imgs, int n_img, int qw, float* ws, const int32_t* map, const float2* tw,
-                         const float4* pre, const DecodeArgs& a, hipStream_t s);
+                         const float4* pre, const DecodeArgs& a, hipStream_t s, CodeType ct = CodeType::kI64);
 void launch_idct_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, void* rgb,
                            PixelType px, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s);
 

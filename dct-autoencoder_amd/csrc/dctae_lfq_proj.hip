@@ -95,8 +95,10 @@ __device__ __forceinline__ void split8h(uint16_t* planes, int plane, int o, f32x
 // k_split_w_h2), two pieces each (A1: one), three products (A1: two) on
 // v_mfma_f32_16x16x32_f16; the dropped terms are <= 3 x 2^-22 |a w|, the
 // accumulator is unscaled exactly before the bias
-template <int NT, int MODE, int WB, bool A1, bool H2>
-__device__ __forceinline__ void lfq_proj_body(const float* __restrict__ x, const int64_t* __restrict__ idx_in,
+// Idx: the type of mode 1's indices, int64_t or int16_t (dctae_codes16.h: an
+// int16 index c means int64(c)); the one load of them is the width's only site
+template <int NT, int MODE, int WB, bool A1, bool H2, typename Idx = int64_t>
+__device__ __forceinline__ void lfq_proj_body(const float* __restrict__ x, const Idx* __restrict__ idx_in,
                                                  int64_t n, int K, int N, const float* __restrict__ w,
                                                  const float* __restrict__ bias, int cd, int ncb, float scale,
                                                  int64_t* __restrict__ idx_out, float* __restrict__ out,
@@ -331,11 +333,12 @@ __device__ __forceinline__ void lfq_proj_body(const float* __restrict__ x, const
   }
 }
 
-#define DCTAE_LFQP_PARAMS                                                                                         \
-  const float *__restrict__ x, const int64_t *__restrict__ idx_in, int64_t n, int K, int N, const float *__restrict__ w, \
+#define DCTAE_LFQP_PARAMS_OF(Idx)                                                                                 \
+  const float *__restrict__ x, const Idx *__restrict__ idx_in, int64_t n, int K, int N, const float *__restrict__ w, \
       const float *__restrict__ bias, int cd, int ncb, float scale, int64_t *__restrict__ idx_out,                    \
       float *__restrict__ out, uint16_t *__restrict__ idx16, InvNorm inv, const uint16_t *__restrict__ wsp, int Kp,     \
       float a_scale, const int *__restrict__ w_exp
+#define DCTAE_LFQP_PARAMS DCTAE_LFQP_PARAMS_OF(int64_t)
 #define DCTAE_LFQP_ARGS x, idx_in, n, K, N, w, bias, cd, ncb, scale, idx_out, out, idx16, inv, wsp, Kp, a_scale, w_exp
 
 template <int NT, int MODE, int WB, bool A1>
@@ -348,6 +351,18 @@ __global__ __launch_bounds__(64 * WB) void k_lfq_proj(DCTAE_LFQP_PARAMS) {
 template <int NT, int MODE, int WB, bool A1>
 __global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(4))) void k_lfq_proj_h2(DCTAE_LFQP_PARAMS) {
   lfq_proj_body<NT, MODE, WB, A1, true>(DCTAE_LFQP_ARGS);
+}
+
+// project_out (mode 1) from int16 indices: the same bodies, the index load apart
+template <int NT, int WB, bool A1>
+__global__ __launch_bounds__(64 * WB) void k_lfq_proj_c16(DCTAE_LFQP_PARAMS_OF(int16_t)) {
+  lfq_proj_body<NT, 1, WB, A1, false, int16_t>(DCTAE_LFQP_ARGS);
+}
+
+template <int NT, int WB, bool A1>
+__global__ __launch_bounds__(64 * WB) __attribute__((amdgpu_waves_per_eu(4))) void k_lfq_proj_h2_c16(
+    DCTAE_LFQP_PARAMS_OF(int16_t)) {
+  lfq_proj_body<NT, 1, WB, A1, true, int16_t>(DCTAE_LFQP_ARGS);
 }
 
 // W (N x K fp32, row-major) -> three bf16 planes [3][NP][Kp], zero padded
@@ -397,13 +412,20 @@ __global__ __launch_bounds__(1024) void k_split_w_h2(const float* __restrict__ w
   if (threadIdx.x == 0) *reinterpret_cast<int*>(ws + 2 * plane) = ex;
 }
 
-template <int MODE, int WB, bool A1, bool H2>
-void launch_nt(int nt, dim3 g, hipStream_t s, const float* x, const int64_t* idx_in, int64_t n, int K, int N,
+template <int MODE, int WB, bool A1, bool H2, typename Idx>
+void launch_nt(int nt, dim3 g, hipStream_t s, const float* x, const Idx* idx_in, int64_t n, int K, int N,
                const float* w, const float* b, int cd, int ncb, float scale, int64_t* idx_out, float* out,
                uint16_t* idx16, InvNorm inv, const uint16_t* wsp, int Kp, float a_scale, const int* w_exp) {
+  constexpr bool C16 = sizeof(Idx) == 2;
+  static_assert(!C16 || MODE == 1, "int16 indices are project_out's input");
 #define DCTAE_LFQP(T) \
-  case T: if (H2) hipLaunchKernelGGL((k_lfq_proj_h2<T, MODE, WB, A1>), g, dim3(64 * WB), 0, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp, Kp, a_scale, w_exp); \
-          else hipLaunchKernelGGL((k_lfq_proj<T, MODE, WB, A1>), g, dim3(64 * WB), 0, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp, Kp, a_scale, w_exp); break;
+  case T: if constexpr (C16) { \
+            if (H2) hipLaunchKernelGGL((k_lfq_proj_h2_c16<T, WB, A1>), g, dim3(64 * WB), 0, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp, Kp, a_scale, w_exp); \
+            else hipLaunchKernelGGL((k_lfq_proj_c16<T, WB, A1>), g, dim3(64 * WB), 0, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp, Kp, a_scale, w_exp); \
+          } else { \
+            if (H2) hipLaunchKernelGGL((k_lfq_proj_h2<T, MODE, WB, A1>), g, dim3(64 * WB), 0, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp, Kp, a_scale, w_exp); \
+            else hipLaunchKernelGGL((k_lfq_proj<T, MODE, WB, A1>), g, dim3(64 * WB), 0, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp, Kp, a_scale, w_exp); \
+          } break;
   switch (nt) {
     DCTAE_LFQP(1) DCTAE_LFQP(2) DCTAE_LFQP(3) DCTAE_LFQP(4) DCTAE_LFQP(5) DCTAE_LFQP(6) DCTAE_LFQP(7)
     DCTAE_LFQP(8) DCTAE_LFQP(9) DCTAE_LFQP(10) DCTAE_LFQP(11) DCTAE_LFQP(12) DCTAE_LFQP(13)
@@ -423,8 +445,8 @@ size_t lfq_proj_scratch_bytes(int N, int K) {
 // fp16 form (H2) for mode 0 when the caller bounds |x| (a_bound > 0, e.g.
 // the PatchNorm clamp of the fused encode), for mode 1 when +-scale is exact
 // in fp16; otherwise the split-bf16 form
-template <int MODE>
-static void launch_mode(int nt, hipStream_t s, const float* x, const int64_t* idx_in, int64_t n, int K, int N,
+template <int MODE, typename Idx = int64_t>
+static void launch_mode(int nt, hipStream_t s, const float* x, const Idx* idx_in, int64_t n, int K, int N,
                         const float* w, const float* b, int cd, int ncb, float scale, int64_t* idx_out, float* out,
                         uint16_t* wsp, uint16_t* idx16 = nullptr, InvNorm inv = InvNorm{}, float a_bound = 0.f,
                         bool ws = false) {
@@ -445,7 +467,7 @@ static void launch_mode(int nt, hipStream_t s, const float* x, const int64_t* id
   if (h2 && ws && lfq_ws_fits(MODE, K, N, cd, ncb)) {   // the W-stationary kernel (dctae_lfq_ws.hip)
     const int NPw = (N + 31) / 32 * 32;
     hipLaunchKernelGGL(k_split_w_h2, dim3(1), dim3(1024), 0, s, w, N, K, NPw, Kp, wsp);
-    launch_lfq_ws(MODE, s, x, idx_in, n, K, N, b, cd, ncb, scale, idx_out, out, idx16, inv.ch, inv.pos, inv.med, inv.b,
+    launch_lfq_ws(MODE, s, x, idx_in, sizeof(Idx) == 2 ? CodeType::kI16 : CodeType::kI64, n, K, N, b, cd, ncb, scale, idx_out, out, idx16, inv.ch, inv.pos, inv.med, inv.b,
                   inv.eps, inv.maxph, inv.maxpw, inv.err, wsp, NPw, Kp, MODE == 0 ? a_scale : 1.0f);
     return;
   }
@@ -453,10 +475,10 @@ static void launch_mode(int nt, hipStream_t s, const float* x, const int64_t* id
     const int* w_exp = reinterpret_cast<const int*>(wsp + 2 * (size_t)NP * Kp);
     hipLaunchKernelGGL(k_split_w_h2, dim3(1), dim3(1024), 0, s, w, N, K, NP, Kp, wsp);
     if constexpr (MODE == 1)
-      launch_nt<MODE, 8, true, true>(nt, g, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp,
+      launch_nt<MODE, 8, true, true, Idx>(nt, g, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp,
                                      Kp, 1.0f, w_exp);
     else
-      launch_nt<MODE, 8, false, true>(nt, g, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv,
+      launch_nt<MODE, 8, false, true, Idx>(nt, g, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv,
                                       wsp, Kp, a_scale, w_exp);
     return;
   }
@@ -472,12 +494,12 @@ static void launch_mode(int nt, hipStream_t s, const float* x, const int64_t* id
   memcpy(&sb, &scale, 4);
   if constexpr (MODE == 1) {
     if ((sb & 0xffffu) == 0) {
-      launch_nt<MODE, 8, true, false>(nt, g, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp,
+      launch_nt<MODE, 8, true, false, Idx>(nt, g, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp,
                                       Kp, 1.0f, nullptr);
       return;
     }
   }
-  launch_nt<MODE, 8, false, false>(nt, g, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp,
+  launch_nt<MODE, 8, false, false, Idx>(nt, g, s, x, idx_in, n, K, N, w, b, cd, ncb, scale, idx_out, out, idx16, inv, wsp,
                                    Kp, 1.0f, nullptr);
 }
 
@@ -486,7 +508,7 @@ static void launch_mode(int nt, hipStream_t s, const float* x, const int64_t* id
 void launch_lfq_project_in(const float* x, int64_t n, int D, const float* w, const float* b, int cd, int ncb,
                            float scale, int64_t* idx, uint16_t* wsp, hipStream_t s, float x_bound, bool ws) {
   if (n <= 0) return;
-  launch_mode<0>((cd * ncb + 15) / 16, s, x, nullptr, n, D, cd * ncb, w, b, cd, ncb, scale, idx, nullptr, wsp, nullptr,
+  launch_mode<0, int64_t>((cd * ncb + 15) / 16, s, x, nullptr, n, D, cd * ncb, w, b, cd, ncb, scale, idx, nullptr, wsp, nullptr,
                  InvNorm{}, x_bound, ws);
 }
 
@@ -495,18 +517,47 @@ void launch_lfq_project_in(const float* x, int64_t n, int D, const float* w, con
 void launch_lfq_project_in16(const float* x, int64_t n, int D, const float* w, const float* b, int cd, int ncb,
                              uint16_t* idx, uint16_t* wsp, hipStream_t s, float x_bound, bool ws) {
   if (n <= 0) return;
-  launch_mode<0>((cd * ncb + 15) / 16, s, x, nullptr, n, D, cd * ncb, w, b, cd, ncb, 0.f, nullptr, nullptr, wsp, idx,
+  launch_mode<0, int64_t>((cd * ncb + 15) / 16, s, x, nullptr, n, D, cd * ncb, w, b, cd, ncb, 0.f, nullptr, nullptr, wsp, idx,
                  InvNorm{}, x_bound, ws);
 }
 
+// lfq.py:187 on n staged raw sign-bit codes, in place (lfq_index_bits): the
+// bits of the quantized value where they differ from the raw ones (scale <= 0)
+__global__ void k_index_bits16(uint16_t* __restrict__ idx, int64_t n, uint32_t pos, uint32_t neg) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+    idx[e] = (uint16_t)lfq_index_bits(idx[e], pos, neg);
+}
+
+// project_in into the caller's int16 indices (dctae_codes16.h, cd <= 15): the
+// 16-bit sink of the encode staging writes the raw sign bits, which are the
+// indices for scale > 0; otherwise the index rule follows in place
+void launch_lfq_project_in_c16(const float* x, int64_t n, int D, const float* w, const float* b, int cd, int ncb,
+                               float scale, int16_t* idx, uint16_t* wsp, hipStream_t s, float x_bound, bool ws) {
+  if (n <= 0) return;
+  launch_lfq_project_in16(x, n, D, w, b, cd, ncb, reinterpret_cast<uint16_t*>(idx), wsp, s, x_bound, ws);
+  if (scale > 0.0f) return;
+  uint64_t pos, neg;
+  lfq_index_masks(scale, cd, &pos, &neg);
+  const int64_t total = n * ncb;
+  const int gx = (int)std::min<int64_t>((total + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_index_bits16, dim3(gx), dim3(256), 0, s, reinterpret_cast<uint16_t*>(idx), total, (uint32_t)pos,
+                     (uint32_t)neg);
+}
+
 // indices (n, ncb) -> codes (+-scale, n x ncb cd) -> out (n, D) = codes w_out^T + b_out; w_out (D, ncb cd)
-void launch_lfq_project_out(const int64_t* idx, int64_t n, int D, const float* w, const float* b, int cd, int ncb,
+// ct: the type of idx (int64 or int16 indices)
+void launch_lfq_project_out(const void* idx, int64_t n, int D, const float* w, const float* b, int cd, int ncb,
                             float scale, float* out, uint16_t* wsp, hipStream_t s, const int64_t* ch, const int64_t* pos,
                             const float* med, const float* nb, float eps, int maxph, int maxpw, int* err, bool h2,
-                            bool ws) {
+                            bool ws, CodeType ct) {
   if (n <= 0) return;
-  launch_mode<1>((D + 15) / 16, s, nullptr, idx, n, cd * ncb, D, w, b, cd, ncb, scale, nullptr, out, wsp, nullptr,
-                 InvNorm{ch, pos, med, nb, eps, maxph, maxpw, err}, h2 ? 1.0f : 0.0f, ws);
+  const InvNorm inv{ch, pos, med, nb, eps, maxph, maxpw, err};
+  if (ct == CodeType::kI16)
+    launch_mode<1>((D + 15) / 16, s, nullptr, static_cast<const int16_t*>(idx), n, cd * ncb, D, w, b, cd, ncb, scale,
+                   nullptr, out, wsp, nullptr, inv, h2 ? 1.0f : 0.0f, ws);
+  else
+    launch_mode<1>((D + 15) / 16, s, nullptr, static_cast<const int64_t*>(idx), n, cd * ncb, D, w, b, cd, ncb, scale,
+                   nullptr, out, wsp, nullptr, inv, h2 ? 1.0f : 0.0f, ws);
 }
 
 }  // namespace dctae

@@ -54,8 +54,10 @@ struct WsInv {
 
 // at most 256 registers per wave: two waves per SIMD (mode 0's 7-wave block;
 // mode 1's two 4-wave blocks per CU)
-template <int MODE, int MT, int NWB>
-__global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(2))) void k_lfq_ws(const float* __restrict__ x, const int64_t* __restrict__ idx_in,
+// Idx: the type of mode 1's indices, int64_t or int16_t (dctae_codes16.h: an
+// int16 index c means int64(c)); the one load of them is the width's only site
+template <int MODE, int MT, int NWB, typename Idx>
+__global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(2))) void k_lfq_ws(const float* __restrict__ x, const Idx* __restrict__ idx_in,
                                                  int64_t n, int K, int N, const float* __restrict__ bias, int cd,
                                                  int ncb, float scale, int64_t* __restrict__ idx_out,
                                                  float* __restrict__ out, uint16_t* __restrict__ idx16, WsInv inv,
@@ -181,7 +183,10 @@ __global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(2))) v
 #pragma unroll
       for (int i = 0; i < RX; ++i) {
         const int64_t f = t * TOK * ncb + tid + kThr * i;
-        rx[i] = reinterpret_cast<const int32_t*>(idx_in)[2 * (f < last ? f : last)];
+        if constexpr (sizeof(Idx) == 8)
+          rx[i] = reinterpret_cast<const int32_t*>(idx_in)[2 * (f < last ? f : last)];
+        else
+          rx[i] = idx_in[f < last ? f : last];
       }
     }
   };
@@ -399,7 +404,7 @@ bool lfq_ws_fits(int mode, int K, int N, int cd, int ncb) {
   return k_ok && n_ok && cd_ok && ncb >= 1 && (int64_t)cd * ncb == (mode == 0 ? N : K);
 }
 
-void launch_lfq_ws(int mode, hipStream_t s, const float* x, const int64_t* idx_in, int64_t n, int K, int N,
+void launch_lfq_ws(int mode, hipStream_t s, const float* x, const void* idx_v, CodeType ct, int64_t n, int K, int N,
                    const float* bias, int cd, int ncb, float scale, int64_t* idx_out, float* out, uint16_t* idx16,
                    const int64_t* ch, const int64_t* pos, const float* med, const float* nb, float eps, int maxph,
                    int maxpw, int* err, const uint16_t* wsp, int NPw, int Kp, float a_scale) {
@@ -413,11 +418,16 @@ void launch_lfq_ws(int mode, hipStream_t s, const float* x, const int64_t* idx_i
   const int64_t per = (ntiles + nb_ - 1) / nb_;
   const int64_t ranges = (ntiles + per - 1) / per;
   const WsInv inv{ch, pos, med, nb, eps, maxph, maxpw, err};
-  if (mode == 0)
-    hipLaunchKernelGGL((k_lfq_ws<0, 2, kNW>), dim3((unsigned)ranges), dim3(64 * kNW), 0, s, x, idx_in, n, K, N, bias,
+  const int64_t* idx_in = static_cast<const int64_t*>(idx_v);
+  if (mode == 1 && ct == CodeType::kI16)
+    hipLaunchKernelGGL((k_lfq_ws<1, 1, 4, int16_t>), dim3((unsigned)(2 * ranges)), dim3(256), 0, s, x,
+                       static_cast<const int16_t*>(idx_v), n, K, N, bias, cd, ncb, scale, idx_out, out, idx16, inv, wsp,
+                       NPw, Kp, a_scale, per);
+  else if (mode == 0)
+    hipLaunchKernelGGL((k_lfq_ws<0, 2, kNW, int64_t>), dim3((unsigned)ranges), dim3(64 * kNW), 0, s, x, idx_in, n, K, N, bias,
                        cd, ncb, scale, idx_out, out, idx16, inv, wsp, NPw, Kp, a_scale, per);
   else
-    hipLaunchKernelGGL((k_lfq_ws<1, 1, 4>), dim3((unsigned)(2 * ranges)), dim3(256), 0, s, x, idx_in, n, K, N, bias,
+    hipLaunchKernelGGL((k_lfq_ws<1, 1, 4, int64_t>), dim3((unsigned)(2 * ranges)), dim3(256), 0, s, x, idx_in, n, K, N, bias,
                        cd, ncb, scale, idx_out, out, idx16, inv, wsp, NPw, Kp, a_scale, per);
 }
 

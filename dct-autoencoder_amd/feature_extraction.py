@@ -408,8 +408,8 @@ class DCTAutoencoderFeatureExtractor:
     @torch.no_grad()
     def encode_batch(self, images, patchnorm=None, lfq=None, batch_size: Optional[int] = None,
                      return_patches: bool = False, return_raw: bool = False, return_scores: bool = False,
-                     ks: Optional[Sequence[int]] = None,
-                     uint8_images: bool = False) -> List[Tuple[DCTPatches, Optional[torch.Tensor]]]:
+                     ks: Optional[Sequence[int]] = None, uint8_images: bool = False,
+                     codes_dtype: torch.dtype = torch.int64) -> List[Tuple[DCTPatches, Optional[torch.Tensor]]]:
         """preprocess every image, pack (iter_batches over ONE dataloader item
         holding all images, FE:179-287), PatchNorm (eval) and LFQ — the
         encode half of SURVEY §3.1-3.3 — in one launch sequence per batch.
@@ -427,7 +427,20 @@ class DCTAutoencoderFeatureExtractor:
         stage hooks, where overridden, are handed those fp32 images.  The
         bytes are read in place; only a non-contiguous image, or a 512-wide
         one at an address that is not 4-byte aligned, is copied first.
+
+        codes_dtype=torch.int16: the codes as int16 (any dtype but int64 and
+        int16 raises TypeError), each the int64 call's code converted with
+        ``.to(torch.int16)`` and so ``codes.long()`` the int64 call's codes;
+        every other output is bit-identical.  The sort / pack kernels store
+        two bytes per code (dctae_encode_c16, include/dctae_codes16.h).  Codes
+        lie in [0, 2^codebook_dim): codebook_dim >= 16 raises ValueError.  On
+        the staged path (an overridden hook) and with projections that are not
+        the fused ones the int16 codes come from a torch conversion: correct,
+        not fast.  The DCTPatches metadata stays int64.
         """
+        _ops.codes_dtype_suffix(codes_dtype, "encode_batch codes_dtype")
+        if codes_dtype == torch.int16 and lfq is not None:
+            _ops.check_codes16(lfq.cfg(), "encode_batch")
         if uint8_images:
             batched = isinstance(images, torch.Tensor) and images.dim() == 4
             if not batched:
@@ -439,7 +452,8 @@ class DCTAutoencoderFeatureExtractor:
                 self._overridden("_batch_groups"):
             if uint8_images:   # the hooks see the fp32 images the bytes mean (dctae_u8_to_f32)
                 images = [_ops.u8_to_f32(self._dev(im)) for im in images]
-            return self._encode_staged(images, patchnorm, lfq, batch_size, return_patches, return_raw)
+            outs = self._encode_staged(images, patchnorm, lfq, batch_size, return_patches, return_raw)
+            return [(dp, c if c is None else c.to(codes_dtype)) for dp, c in outs]
         if isinstance(images, torch.Tensor) and images.dim() == 4:
             x = self._dev(images)
             B, _, H, W = x.shape
@@ -473,12 +487,13 @@ class DCTAutoencoderFeatureExtractor:
                 if len(plan.images) != len(ks) else plan
             res = _ops.encode(sub, dev, self.params(), plan_local, plan.n_rows, self.max_seq_len, norm, lcfg,
                               want_codes=lcfg is not None, want_patches=want_norm, want_raw=return_raw,
-                              want_scores=return_scores)
+                              want_scores=return_scores, codes_dtype=codes_dtype)
             if proj:   # codes only: lfq.py:136-187 without the quantized output's project_out
                 # fused project_in + sign + pack on the PatchNorm output, whose clamp
                 # (patchnorm.py:163) bounds it: the kernels of BatchEncoder's staged path
                 xb = max(abs(norm.min_val), abs(norm.max_val))
-                res["codes"] = lfq.project_codes(res["patches"], x_bound=xb if 0.0 < xb < math.inf else None)
+                res["codes"] = lfq.project_codes(res["patches"], x_bound=xb if 0.0 < xb < math.inf else None,
+                                                 codes_dtype=codes_dtype)
             pt = res["patches"] if return_patches else res.get("raw")
             if pt is None:
                 pt = torch.empty((plan.n_rows, self.max_seq_len, 0), device=dev)
@@ -535,8 +550,15 @@ class DCTAutoencoderFeatureExtractor:
         (the decode half of SURVEY §3.4 without the transformer).  With LFQ
         projections the codes go through the fused codes -> project_out kernel and the HIP
         inverse PatchNorm first, and the fused decode starts from the tokens.
-        output_dtype=torch.uint8: uint8 images, as postprocess gives them."""
+        output_dtype=torch.uint8: uint8 images, as postprocess gives them.
+        codes: int64, or int16 (an int16 code c means int64(c); read two bytes
+        per code by the kernels, no widened copy; every pixel is bit-identical
+        to the decode of ``codes.long()``).  Any other dtype raises TypeError;
+        int16 codes with codebook_dim >= 16 raise ValueError."""
         _ops.out_dtype_suffix(output_dtype, "decode_batch output_dtype")
+        _ops.codes_dtype_suffix(codes.dtype, "decode_batch codes")
+        if codes.dtype == torch.int16:
+            _ops.check_codes16(lfq.cfg(), "decode_batch")
         staged = self._staged_out()   # an overridden revert_patching / _transform_image_out (FE:289-310)
         if lfq.has_projections or staged:
             dp = dct_patches.shallow_copy()
@@ -565,12 +587,17 @@ class BatchEncoder:
     built once; each call only enqueues the kernels (dctae_encode).
     input_dtype=torch.uint8: the calls take (B, 3, H, W) uint8 bytes meaning
     ``u8.float() / 255`` (dctae_encode_u8 / dctae_encode_lfq_proj_u8), outputs
-    bit-identical to the fp32 encoder's on that tensor."""
+    bit-identical to the fp32 encoder's on that tensor.
+    codes_dtype=torch.int16: ``out["codes"]`` is int16, each code the int64
+    encoder's converted (the ``_c16`` entries of include/dctae_codes16.h; any
+    other dtype raises TypeError, codebook_dim >= 16 ValueError); every other
+    output the same."""
 
     def __init__(self, fe: DCTAutoencoderFeatureExtractor, batch: int, height: int, width: int, patchnorm, lfq,
-                 device=None, want_patches: bool = False, input_dtype: torch.dtype = torch.float32):
+                 device=None, want_patches: bool = False, input_dtype: torch.dtype = torch.float32,
+                 codes_dtype: torch.dtype = torch.int64):
         import ctypes as C
-        from ._lib import Images, LFQCfg, Packing, PackedOut, i32, i64, ptr
+        from ._lib import Images, LFQCfg, Packing, PackedOut, PackedOut16, i32, i64, ptr
         self.fe = fe
         self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.dev.index is None:   # "cuda" -> the current device, as tensors report it
@@ -579,7 +606,11 @@ class BatchEncoder:
         if input_dtype not in (torch.float32, torch.uint8):
             raise TypeError(f"BatchEncoder input_dtype: torch.float32 or torch.uint8, got {input_dtype}")
         self.input_dtype = input_dtype
-        self._sfx = "_u8" if input_dtype == torch.uint8 else ""
+        self.codes_dtype = codes_dtype
+        self._sfx = ("_u8" if input_dtype == torch.uint8 else "") + \
+            _ops.codes_dtype_suffix(codes_dtype, "BatchEncoder codes_dtype")
+        if codes_dtype == torch.int16:
+            _ops.check_codes16(lfq.cfg(), "BatchEncoder")
         if fe.sample_patches_beta > 0:
             raise AssertionError("BatchEncoder needs sample_patches_beta == 0 (fixed k)")
         k = fe._tokens(height, width)
@@ -611,7 +642,7 @@ class BatchEncoder:
         self.packing = Packing(*[C.cast(a, C.POINTER(C.c_int32)) for a in self._pk_keep], self.n_rows)
         R, S = self.n_rows, self.S
         self.out = {
-            "codes": torch.empty((R, S, self.lcfg.num_codebooks), dtype=torch.long, device=self.dev),
+            "codes": torch.empty((R, S, self.lcfg.num_codebooks), dtype=codes_dtype, device=self.dev),
             "positions": torch.empty((R, S, 2), dtype=torch.long, device=self.dev),
             "channels": torch.empty((R, S), dtype=torch.long, device=self.dev),
             "image_ids": torch.empty((R, S), dtype=torch.long, device=self.dev),
@@ -620,7 +651,7 @@ class BatchEncoder:
         if want_norm:
             self.out["patches"] = torch.empty((R, S, fe.patch_size ** 2), dtype=torch.float32, device=self.dev)
         o = self.out
-        self.po = PackedOut(ptr(None if self.proj and not self.proj_staged else o["codes"]), ptr(o["positions"]), ptr(o["channels"]), ptr(o["image_ids"]),
+        self.po = (PackedOut16 if codes_dtype == torch.int16 else PackedOut)(ptr(None if self.proj and not self.proj_staged else o["codes"]), ptr(o["positions"]), ptr(o["channels"]), ptr(o["image_ids"]),
                             ptr(o["key_pad_mask"]), ptr(o.get("patches")), None, None)
         self._ncfg = self.norm.c()
         self._cfg = self.p.c(S)
@@ -653,7 +684,8 @@ class BatchEncoder:
         if self.proj:
             w, b = self.lfq._proj_w(self.lfq.project_in, self.dev)
             from . import _ops
-            self.out["codes"] = _ops.lfq_project_in_into(self.out["patches"], w, b, self.lcfg, self.out["codes"])
+            self.out["codes"] = _ops.lfq_project_in_into(self.out["patches"], w, b, self.lcfg, self.out["codes"],
+                                                         codes_dtype=self.codes_dtype)
         return self.out
 
 
@@ -665,7 +697,10 @@ class BatchDecoder:
     order, image ids ascending, FE:619-633) into one (B, 3, H, W) tensor.
     output_dtype=torch.uint8: ``out`` is a (B, 3, H, W) uint8 tensor written by
     the decode itself (dctae_decode_u8 / dctae_decode_normed_u8), every byte the
-    fp32 decoder's value through ``mul(255).add(0.5).clamp(0, 255)`` truncated."""
+    fp32 decoder's value through ``mul(255).add(0.5).clamp(0, 255)`` truncated.
+    ``packed["codes"]``: int64, or int16 read as it is (the ``_c16`` entries of
+    include/dctae_codes16.h; pixels bit-identical to those from
+    ``codes.long()``); any other dtype raises TypeError."""
 
     def __init__(self, enc: "BatchEncoder", patchnorm, lfq, output_dtype: torch.dtype = torch.float32):
         _ops.out_dtype_suffix(output_dtype, "BatchDecoder output_dtype")
@@ -695,6 +730,9 @@ class BatchDecoder:
 
     def __call__(self, packed) -> torch.Tensor:
         e = self.enc
+        _ops.codes_dtype_suffix(packed["codes"].dtype, "BatchDecoder codes")
+        if packed["codes"].dtype == torch.int16:
+            _ops.check_codes16(self.lcfg, "BatchDecoder")
         if not self.proj:
             return self._decode(packed, self._ncfg, self.lcfg, packed["codes"], None)
         if not self.lfq._fused_proj():

@@ -115,17 +115,24 @@ class LFQ(nn.Module):
             return None if t is None else t.detach().to(device=dev, dtype=torch.float32).contiguous()
         return f32(lin.weight), f32(lin.bias)
 
-    def project_codes(self, x, x_bound=None):
+    def project_codes(self, x, x_bound=None, codes_dtype=torch.int64):
         """Indices only (the encode path): x (..., dim) -> (..., num_codebooks),
         project_in fused with the sign / packing when there are projections.
         x_bound: |x| <= x_bound is known (the PatchNorm clamp in
-        encode_batch): the fp16 kernels, as the fused BatchEncoder path."""
+        encode_batch): the fp16 kernels, as the fused BatchEncoder path.
+        codes_dtype=torch.int16: the indices as int16, each the int64 index
+        converted (codebook_dim <= 15, else ValueError); written as int16 by
+        the fused kernel, by a torch conversion (correct, not fast) where the
+        projections are not the fused ones."""
+        _ops.codes_dtype_suffix(codes_dtype, "project_codes codes_dtype")
+        if codes_dtype == torch.int16:
+            _ops.check_codes16(self.cfg(), "project_codes")
         if self._fused_proj():
             w, b = self._proj_w(self.project_in, x.device)
-            return _ops.lfq_project_in(x, w, b, self.cfg(self.project_in.weight.dtype), x_bound)
+            return _ops.lfq_project_in(x, w, b, self.cfg(self.project_in.weight.dtype), x_bound, codes_dtype)
         h = self.project_in(x)
         _, idx = _ops.lfq_forward(h, self.cfg(h.dtype), want_quantized=False)
-        return idx
+        return idx.to(codes_dtype)
 
     def cfg(self, dtype=None) -> LFQCfg:
         """Kernel config.  ``dtype``: the dtype the reference forms
