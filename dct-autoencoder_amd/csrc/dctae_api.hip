@@ -99,9 +99,9 @@ int OrderedCall::scratch_bytes(Scratch which, size_t bytes, uint8_t** out) {
   const bool grew = bytes > b.cap;
   if (int rc = b.grow(ctx, bytes, kScratchName[which])) return rc;
   *out = b.p;
-  // ws_poison: the workspace and the staging are filled when this call first
-  // asks for them (and when it grows them), never over what it wrote since
-  if (ctx->opt.ws_poison && which <= kStage && b.p && (grew || !(poisoned & (1u << which)))) {
+  // ws_poison: each of the five buffers is filled when this call first asks
+  // for it (and when it grows it), never over what it wrote since
+  if (ctx->opt.ws_poison && b.p && (grew || !(poisoned & (1u << which)))) {
     poisoned |= 1u << which;
     HIPCHK(ctx, hipDeviceSynchronize());
     HIPCHK(ctx, hipMemset(b.p, 0xff, b.cap));

@@ -88,9 +88,10 @@ struct Options {
   int64_t cols_dma = 1;
   // images with both passes on the GEMM DCT: T / Y parity-planar (ImgDesc::tperm)
   int64_t tperm = 1;
-  // debug: fill the workspace and staging buffers with NaN bits (0xff) before
-  // every call that sizes them, so a read of a word the call did not write
-  // shows in its outputs (env DCTAE_WS_POISON=1 sets it at context creation)
+  // debug: fill each of the five scratch buffers (workspace, staging, PatchNorm
+  // statistics, VectorQuantize, LFQ projection) with NaN bits (0xff) when a
+  // call first asks for it, so a read of a word the call did not write shows
+  // in its outputs (env DCTAE_WS_POISON=1 sets it at context creation)
   int64_t ws_poison = 0;
   // LFQ projections on the fp16 form with the conf/patch14-l.json shapes
   // (192 < in, out <= 208 / 224): 1 = the W-stationary kernel k_lfq_ws

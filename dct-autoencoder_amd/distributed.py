@@ -92,6 +92,5 @@ def train_step(pn, dct_patches, group=None, ops: Optional[StatsOps] = None) -> t
                            pn.b.data.float().contiguous(), dp.patches, dp.patch_channels, dp.patch_positions,
                            dp.key_pad_mask, ops, group)
     pn.n.data, pn.median.data, pn.b.data = n, med, b
-    pn._thr_cache = None
     return torch.where(dp.key_pad_mask.unsqueeze(-1), torch.zeros((), dtype=dp.patches.dtype,
                                                                    device=dp.patches.device), dp.patches)

@@ -632,7 +632,8 @@ class BatchEncoder:
         self.proj_staged = (self.proj and all(n == fe.max_seq_len for n in self.plan.row_len)
                             and lfq.codebook_dim <= 16 and (fe.patch_size ** 2) % 4 == 0)
         want_norm = want_patches or (self.proj and not self.proj_staged)
-        self.norm = patchnorm.state(thresholds=not want_norm)
+        self.patchnorm, self._thr = patchnorm, not want_norm
+        self._take_norm()
         self.lcfg = lfq.cfg()
         self.p = fe.params()
         per = 3 * height * width
@@ -653,16 +654,25 @@ class BatchEncoder:
         o = self.out
         self.po = (PackedOut16 if codes_dtype == torch.int16 else PackedOut)(ptr(None if self.proj and not self.proj_staged else o["codes"]), ptr(o["positions"]), ptr(o["channels"]), ptr(o["image_ids"]),
                             ptr(o["key_pad_mask"]), ptr(o.get("patches")), None, None)
-        self._ncfg = self.norm.c()
         self._cfg = self.p.c(S)
         from . import _lib
         self.ctx = _lib.context(self.dev)
+
+    def _take_norm(self):
+        """The PatchNorm tables (and thresholds) as they are now; taken again
+        only when the module's stamp has moved (an in-place update, a
+        load_state_dict, a training step, another eps or clamp)."""
+        self._norm_stamp = self.patchnorm._stamp()
+        self.norm = self.patchnorm.state(thresholds=self._thr)
+        self._ncfg = self.norm.c()
 
     def __call__(self, x: torch.Tensor):
         import ctypes as C
         from ._lib import Images, ImagesU8, ptr, stream_ptr
         assert x.shape == (self.B, 3, self.H, self.W) and x.dtype == self.input_dtype and x.is_contiguous()
         assert x.device == self.dev
+        if self.patchnorm._stamp() != self._norm_stamp:   # host compare; unchanged tables add no device work
+            self._take_norm()
         u8 = self.input_dtype == torch.uint8
         if u8 and self.W == 512 and x.data_ptr() % 4:   # the 512-wide row kernel's dword loads (include/dctae_u8.h)
             x = x.clone()
@@ -709,10 +719,9 @@ class BatchDecoder:
         pl, p = enc.plan, enc.fe.patch_size
         self.table = _ops.DecodeTable.from_layout(enc.p, enc.dev, enc.n_rows, enc.S, pl.row, pl.local_id,
                                                   (enc.H, enc.W), (enc.H // p, enc.W // p))
-        self.norm = patchnorm.state(thresholds=False)
-        self._ncfg = self.norm.c()
-        self.lcfg = lfq.cfg()
         self.lfq, self.patchnorm = lfq, patchnorm
+        self._take_norm()
+        self.lcfg = lfq.cfg()
         self.proj = lfq.has_projections
         # LFQ with projections (lfq.py:54-62).  True: project_out alone (dctae_lfq_project_out) and the inverse
         # PatchNorm inside the decode's column kernel (dctae_decode_normed: per-block (c, strip) tables instead
@@ -728,8 +737,16 @@ class BatchDecoder:
                           self.output_dtype)
         return self.out
 
+    def _take_norm(self):
+        """As BatchEncoder._take_norm: the tables now, retaken when the stamp moves."""
+        self._norm_stamp = self.patchnorm._stamp()
+        self.norm = self.patchnorm.state(thresholds=False)
+        self._ncfg = self.norm.c()
+
     def __call__(self, packed) -> torch.Tensor:
         e = self.enc
+        if self.patchnorm._stamp() != self._norm_stamp:
+            self._take_norm()
         _ops.codes_dtype_suffix(packed["codes"].dtype, "BatchDecoder codes")
         if packed["codes"].dtype == torch.int16:
             _ops.check_codes16(self.lcfg, "BatchDecoder")

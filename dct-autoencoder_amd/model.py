@@ -49,6 +49,7 @@ from torch import nn
 
 from . import _lib
 from . import model_train as _train
+from ._tracked import _TrackedParameter, _param_stamp   # noqa: F401  (optim imports the stamp from here)
 from .dct_patches import DCTPatches
 from .lfq import LFQ
 from .losses import compute_entropy_loss
@@ -154,41 +155,6 @@ def _bf16_padded(w: torch.Tensor, kp: int) -> torch.Tensor:
 
 
 _pack_generation = itertools.count(1)
-
-
-class _TrackedParameter(nn.Parameter):
-    """The nn.Parameter of a Linear that ``_Packed`` copies, counting accesses of ``.data``.
-    torch gives ``p.data`` a version counter of its own, so ``p.data.copy_(...)`` moves
-    neither ``p._version`` nor ``p.data_ptr()``; the count is the third part of
-    ``_param_stamp``, so the packed bf16 copies are rebuilt after any access that may have
-    been such a write (a read costs one rebuild, never a stale pack).  A tensor obtained from
-    ``.data`` earlier and written later is not seen.  Pickling gives back a plain Parameter."""
-    _data_reads = 0
-
-    @property
-    def data(self):
-        self._data_reads += 1
-        return torch.Tensor.data.__get__(self)
-
-    @data.setter
-    def data(self, value):
-        self._data_reads += 1
-        torch.Tensor.data.__set__(self, value)
-
-    def __deepcopy__(self, memo):   # nn.Parameter's, without going through .data
-        if id(self) in memo:
-            return memo[id(self)]
-        result = type(self)(self.detach().clone(memory_format=torch.preserve_format), self.requires_grad)
-        memo[id(self)] = result
-        return result
-
-    def __repr__(self):
-        return "Parameter containing:\n" + repr(self.detach().as_subclass(torch.Tensor))
-
-
-def _param_stamp(p):
-    """What identifies a parameter's current value to the pack caches."""
-    return p.data_ptr(), p._version, getattr(p, "_data_reads", 0)
 
 
 def _packed_linears(model: "DCTAutoencoder"):

@@ -13,6 +13,7 @@ from torch import nn
 
 from . import _ops
 from ._ops import FEParams, NormState
+from ._tracked import _param_stamp, _track
 from .dct_patches import DCTPatches
 
 
@@ -41,21 +42,42 @@ class PatchNorm(nn.Module):
         return FEParams(channels=self.channels, patch_size=self.patch_size, max_patch_h=self.max_patch_h,
                         max_patch_w=self.max_patch_w)
 
+    def _stamp(self):
+        """What identifies the tables' current values to the caches that copy
+        them (the LFQ thresholds here; BatchEncoder / BatchDecoder).  median
+        and b are tracked parameters (_tracked.py): an in-place op moves
+        ``_version``, a write through ``.data`` its access count, a new
+        tensor the pointer; a Parameter object that is not tracked yet (a new
+        one, or one from a pickle) is made so and counted.  Host work only.
+        Not a pure read: it is also where an untracked Parameter becomes a
+        tracked one (its ``__class__`` is swapped in place, as model.py does
+        for the Linears) and ``_retracked`` counts those swaps, so that a new
+        Parameter object at a reused address still moves the stamp.  A module
+        from an older pickle has no ``_retracked`` yet, hence the getattr."""
+        retracked = getattr(self, "_retracked", 0)
+        if _track(self.median) | _track(self.b):
+            retracked += 1
+            self._retracked = retracked
+        return (_param_stamp(self.median), _param_stamp(self.b), retracked, float(self.eps),
+                float(self.min_val), float(self.max_val))
+
     def state(self, thresholds: bool = False) -> NormState:
         """Device view of the tables handed to the kernels.  With thresholds,
         the exact LFQ-bit thresholds (one compare per element instead of a
         subtract + divide + two table reads) are attached; they are cached
-        and rebuilt whenever median / b / eps / clamp change."""
-        med = self.median.data
-        b = self.b.data
+        and rebuilt whenever median / b / eps / clamp change (``_stamp``).
+        The tables are taken with ``detach()``, never through ``.data``,
+        which would move the stamp."""
+        stamp = self._stamp()
+        med = self.median.detach()
+        b = self.b.detach()
         if med.dtype != torch.float32 or b.dtype != torch.float32:
             raise AssertionError("PatchNorm tables must be float32 on the MI355X path")
         st = NormState(med.contiguous(), b.contiguous(), float(self.eps), float(self.min_val), float(self.max_val))
         if thresholds and med.is_cuda:
-            key = (med.data_ptr(), b.data_ptr(), med._version, b._version, st.eps, st.min_val, st.max_val)
             cache = getattr(self, "_thr_cache", None)
-            if cache is None or cache[0] != key:
-                cache = (key, _ops.norm_thresholds(st))
+            if cache is None or cache[0] != stamp:
+                cache = (stamp, _ops.norm_thresholds(st))
                 self._thr_cache = cache
             st.thr = cache[1]
         return st

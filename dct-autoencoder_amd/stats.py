@@ -37,5 +37,4 @@ def train_step(pn, dct_patches) -> torch.Tensor:
     pn.n.data = n
     pn.median.data = median
     pn.b.data = b
-    pn._thr_cache = None
     return out.view(dct_patches.patches.shape)

@@ -538,9 +538,11 @@ int dctae_set_chunk_bytes(dctae_ctx* ctx, int64_t bytes);
  * "gemm_dma" (1, default: the encode's row GEMM on
  * k_gemm_h2r, both operands streamed into a two-stage LDS ring by
  * buffer_load ... lds; 0: k_gemm_h2's register staging; outputs
- * bit-identical), "ws_poison" (0, default; 1: a debug check that fills the
- * workspace and staging buffers with NaN bits once per call, before the
- * call's first use of them, so a read of a word the call did not write shows
+ * bit-identical), "ws_poison" (0, default; 1: a debug check that fills each of
+ * the context's five scratch buffers -- workspace, staging, PatchNorm
+ * statistics scratch, VectorQuantize scratch, LFQ projection scratch -- with
+ * NaN bits once per call, before the call's first use of that buffer (and
+ * when the call grows it), so a read of a word the call did not write shows
  * in its outputs;
  * also set by the environment variable DCTAE_WS_POISON=1 at context
  * creation; slow).  Profiling builds only (make PROFILING=1; the shipped
