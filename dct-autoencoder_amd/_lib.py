@@ -55,6 +55,12 @@ class ImagesU8(C.Structure):
                 ("n_img", C.c_int32)]
 
 
+class ImagesOut(C.Structure):
+    """dctae_images_out (include/dctae_resize.h): fp32 output images, img_off in floats"""
+    _fields_ = [("rgb_dev", C.c_void_p), ("img_off", C.POINTER(C.c_int64)), ("hw", C.POINTER(C.c_int32)),
+                ("n_img", C.c_int32)]
+
+
 class Packing(C.Structure):
     _fields_ = [("row", C.POINTER(C.c_int32)), ("col", C.POINTER(C.c_int32)), ("k", C.POINTER(C.c_int32)),
                 ("local_id", C.POINTER(C.c_int32)), ("row_len", C.POINTER(C.c_int32)), ("n_rows", C.c_int32)]
@@ -115,6 +121,9 @@ _SIGS = {
     "dctae_spectrum_tokens_u8": ([_P, C.POINTER(FECfg), C.POINTER(ImagesU8), C.POINTER(C.c_int64), _P, _P, _P],
                                  C.c_int),
     "dctae_u8_to_f32": ([_P, _P, C.c_int64, _P, _P], C.c_int),
+    # include/dctae_resize.h: the antialiased resize of a ragged image list
+    "dctae_resize_aa": ([_P, C.POINTER(Images), C.POINTER(ImagesOut), _P], C.c_int),
+    "dctae_resize_aa_u8": ([_P, C.POINTER(ImagesU8), C.POINTER(ImagesOut), _P], C.c_int),
     "dctae_dct2": ([_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P], C.c_int),
     "dctae_patch_spectrum": ([_P, C.POINTER(FECfg), _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P],
                              C.c_int),

@@ -39,6 +39,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _ops, packing
+from . import resize as _resize
 from ._ops import FEParams
 from .dct_patches import DCTPatches
 
@@ -173,8 +174,14 @@ class DCTAutoencoderFeatureExtractor:
                     patch_sizes=patch_size)
 
     @torch.no_grad()
-    def preprocess_many(self, images: Sequence[torch.Tensor]) -> List[Dict[str, Any]]:
-        """``preprocess`` for several images in one launch sequence."""
+    def preprocess_many(self, images: Sequence[torch.Tensor], dataset_crop: bool = False) -> List[Dict[str, Any]]:
+        """``preprocess`` for several images in one launch sequence.
+        dataset_crop=True: the images go through ``self.dataset_crop`` first
+        (fp32 or uint8 images; the stages see the resized fp32 images)."""
+        if dataset_crop:
+            images = self.dataset_crop(images)
+            if images and images[0].dtype == torch.uint8:   # none needed the resize: the fp32 images the bytes mean
+                images = [_ops.u8_to_f32(im) for im in images]
         if self._staged_in() or any(im.dtype != torch.float32 for im in images):
             # fp16 / bf16 images: the reference's stage sequence, whose colour
             # transform runs in the input dtype (FE:135-141)
@@ -404,12 +411,28 @@ class DCTAutoencoderFeatureExtractor:
                            x.patch_positions, x.patch_channels, x.patch_sizes, x.original_sizes,
                            patches=x.patches, out_dtype=output_dtype)
 
+    # ------------------------------------------------------------ dataset crop
+    @property
+    def dataset_max_size(self) -> int:
+        """the reference's dataset.py:53-57 for this extractor: max(patch_size * max(max_patch_w, max_patch_h), 768)"""
+        return _resize.dataset_max_size(self.patch_size, self.max_patch_h, self.max_patch_w)
+
+    @torch.no_grad()
+    def dataset_crop(self, images: Sequence[torch.Tensor], max_size: Optional[int] = None) -> List[torch.Tensor]:
+        """The reference's dataset crop (dataset.py:59-73) for a list of
+        (3, H, W) fp32 or uint8 images: every image with a side above max_size
+        (default ``self.dataset_max_size``) is shrunk by the antialiased
+        bilinear resize, all in one launch (resize.dataset_crop)."""
+        images = [self._dev(im) if isinstance(im, torch.Tensor) else im for im in images]
+        return _resize.dataset_crop(images, self.dataset_max_size if max_size is None else max_size)
+
     # ------------------------------------------------------- fused MI355X path
     @torch.no_grad()
     def encode_batch(self, images, patchnorm=None, lfq=None, batch_size: Optional[int] = None,
                      return_patches: bool = False, return_raw: bool = False, return_scores: bool = False,
                      ks: Optional[Sequence[int]] = None, uint8_images: bool = False,
-                     codes_dtype: torch.dtype = torch.int64) -> List[Tuple[DCTPatches, Optional[torch.Tensor]]]:
+                     codes_dtype: torch.dtype = torch.int64,
+                     dataset_crop: bool = False) -> List[Tuple[DCTPatches, Optional[torch.Tensor]]]:
         """preprocess every image, pack (iter_batches over ONE dataloader item
         holding all images, FE:179-287), PatchNorm (eval) and LFQ — the
         encode half of SURVEY §3.1-3.3 — in one launch sequence per batch.
@@ -437,6 +460,14 @@ class DCTAutoencoderFeatureExtractor:
         the staged path (an overridden hook) and with projections that are not
         the fused ones the int16 codes come from a torch conversion: correct,
         not fast.  The DCTPatches metadata stays int64.
+
+        dataset_crop=True: the images go through ``self.dataset_crop`` first
+        (the reference's dataset.py:59-73, one resize launch for all of them),
+        and every output is bit-identical to the call on
+        ``self.dataset_crop(images)``.  Byte images that needed a resize
+        continue as the fp32 images it wrote; where none did, the bytes are
+        encoded in place as without the option.  The stage hooks, where
+        overridden, are handed the resized fp32 images.
         """
         _ops.codes_dtype_suffix(codes_dtype, "encode_batch codes_dtype")
         if codes_dtype == torch.int16 and lfq is not None:
@@ -448,6 +479,13 @@ class DCTAutoencoderFeatureExtractor:
             for im in ([images] if batched else images):
                 if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8:
                     raise TypeError(f"uint8_images=True needs uint8 tensors, got {getattr(im, 'dtype', type(im))}")
+        if dataset_crop:
+            if isinstance(images, torch.Tensor) and images.dim() == 4:
+                if _resize.dataset_crop_size(images.shape[2], images.shape[3], self.dataset_max_size) is not None:
+                    images = list(images.unbind(0))
+            if not isinstance(images, torch.Tensor):
+                images = self.dataset_crop(images)
+                uint8_images = uint8_images and bool(images) and images[0].dtype == torch.uint8
         if self._staged_in() or self._overridden("_group_patches_by_max_seq_len") or \
                 self._overridden("_batch_groups"):
             if uint8_images:   # the hooks see the fp32 images the bytes mean (dctae_u8_to_f32)
