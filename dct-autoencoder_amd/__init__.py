@@ -16,10 +16,13 @@ from .optim import FusedAdamW  # noqa: F401
 from .patchnorm import PatchNorm  # noqa: F401
 from .vector_quantize import VectorQuantize  # noqa: F401
 from . import packing  # noqa: F401
+from . import progressive  # noqa: F401
+from .progressive import frame_cuts, image_clip  # noqa: F401
 from . import shards  # noqa: F401
 
 __all__ = ["DCTAutoencoderFeatureExtractor", "DCTPatches", "PatchNorm", "LFQ", "VectorQuantize", "to_dict", "from_dict",
            "DCTAutoencoder", "DCTAutoencoderConfig", "CLIPEncoderConfig", "FusedAdamW",
            "GroupPatchesState", "build_attn_mask", "load_library", "DCTAEError", "DCTAEUnavailable",
            "LFQDistance", "compute_entropy_loss", "masked_mean", "calculate_perplexity",
-           "reconstruction_losses", "masked_perplexity", "step_losses", "pixel_loss"]
+           "reconstruction_losses", "masked_perplexity", "step_losses", "pixel_loss", "progressive", "frame_cuts",
+           "image_clip"]

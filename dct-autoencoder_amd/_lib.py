@@ -61,6 +61,18 @@ class ImagesOut(C.Structure):
                 ("n_img", C.c_int32)]
 
 
+class Frames(C.Structure):
+    """dctae_frames (include/dctae_frames.h): the prefix frames of one call, host arrays"""
+    _fields_ = [("n_frames", C.c_int32), ("img", C.POINTER(C.c_int32)), ("cut", C.POINTER(C.c_int32)),
+                ("out_off", C.POINTER(C.c_int64))]
+
+
+# the type tags of include/dctae_frames.h
+PIXEL_F32, PIXEL_U8 = 0, 1
+CODES_I64, CODES_I16 = 0, 1
+CLIP_NONE, CLIP_MINMAX = 0, 1
+
+
 class Packing(C.Structure):
     _fields_ = [("row", C.POINTER(C.c_int32)), ("col", C.POINTER(C.c_int32)), ("k", C.POINTER(C.c_int32)),
                 ("local_id", C.POINTER(C.c_int32)), ("row_len", C.POINTER(C.c_int32)), ("n_rows", C.c_int32)]
@@ -124,6 +136,13 @@ _SIGS = {
     # include/dctae_resize.h: the antialiased resize of a ragged image list
     "dctae_resize_aa": ([_P, C.POINTER(Images), C.POINTER(ImagesOut), _P], C.c_int),
     "dctae_resize_aa_u8": ([_P, C.POINTER(ImagesU8), C.POINTER(ImagesOut), _P], C.c_int),
+    # include/dctae_frames.h: the prefix frames of a packed batch, image_clip
+    "dctae_decode_frames": ([_P, C.POINTER(FECfg), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P, _P, C.POINTER(Frames),
+                             C.POINTER(Norm), C.POINTER(LFQCfg), _P, C.c_int32, _P, C.c_int32, C.c_int32, _P,
+                             C.c_int32, _P], C.c_int),
+    "dctae_image_clip": ([_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P, C.POINTER(C.c_int64), _P,
+                          C.c_int32, _P], C.c_int),
     "dctae_dct2": ([_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P], C.c_int),
     "dctae_patch_spectrum": ([_P, C.POINTER(FECfg), _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P],
                              C.c_int),

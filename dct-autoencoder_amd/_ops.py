@@ -672,7 +672,8 @@ class DecodeTable:
     the batch tensors in the layout the library reads.  Building it from the
     batch walks ``ids.cpu()``: the one host synchronisation of a decode."""
 
-    def __init__(self, p: FEParams, ids, key_pad, positions, channels, patch_sizes, original_sizes):
+    def __init__(self, p: FEParams, ids, key_pad, positions, channels, patch_sizes, original_sizes, ids_host=None):
+        """ids_host: ``ids`` on the host when the caller has read them already (no second read)"""
         self.dev = _check_dev(ids, key_pad, positions, channels)
         self.R, self.S = ids.shape
         self.ids = ids.long().contiguous()
@@ -680,7 +681,7 @@ class DecodeTable:
         self.pos = positions.long().contiguous()
         self.ch = channels.long().contiguous()
         # image enumeration: rows in order, ids ascending (FE:619-633); host view
-        ids_h = self.ids.cpu()
+        ids_h = self.ids.cpu() if ids_host is None else ids_host
         places = [(r, im) for r in range(self.R) for im in torch.unique(ids_h[r]).tolist()]
         if len(places) > len(patch_sizes) or len(places) > len(original_sizes):
             raise IndexError("more images in the batch than patch_sizes / original_sizes entries")

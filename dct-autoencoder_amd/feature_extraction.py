@@ -618,6 +618,30 @@ class DCTAutoencoderFeatureExtractor:
                            dct_patches.patch_sizes, dct_patches.original_sizes, codes=codes,
                            norm=patchnorm.state(), lfq=lfq.cfg(), out_dtype=output_dtype)
 
+    # ------------------------------------------------------------ progressive decode
+    def postprocess_prefixes(self, x: DCTPatches, prefixes, output_dtype: torch.dtype = torch.float32,
+                             clip=None) -> List[List[torch.Tensor]]:
+        """The token-prefix frames of every image of un-normalised DCTPatches in
+        one launch sequence (progressive.postprocess_prefixes): frame (i, k) is,
+        bit for bit, image i of ``postprocess`` with all but the image's first
+        min(k, n_i) real tokens padded.  prefixes: ints for every image, or one
+        sequence per image; clip: None or "minmax" (``image_clip`` of every frame)."""
+        from . import progressive
+        return progressive.postprocess_prefixes(self, x, prefixes, output_dtype, clip)
+
+    def decode_prefixes(self, dct_patches: DCTPatches, codes: torch.Tensor, patchnorm, lfq, prefixes,
+                        output_dtype: torch.dtype = torch.float32, clip=None) -> List[List[torch.Tensor]]:
+        """postprocess_prefixes from LFQ codes, on ``decode_batch``'s branches (progressive.decode_prefixes)."""
+        from . import progressive
+        return progressive.decode_prefixes(self, dct_patches, codes, patchnorm, lfq, prefixes, output_dtype, clip)
+
+    def image_clip(self, images: Sequence[torch.Tensor], output_dtype: torch.dtype = torch.float32
+                   ) -> List[torch.Tensor]:
+        """util.py:143-147 on a list of (3, H, W) fp32 device images of any sizes, in one launch sequence
+        (progressive.image_clip_many)."""
+        from . import progressive
+        return progressive.image_clip_many(images, output_dtype)
+
 
 class BatchEncoder:
     """Pre-planned fused encode for a fixed batch geometry (the bench and
