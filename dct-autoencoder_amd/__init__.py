@@ -17,7 +17,7 @@ from .patchnorm import PatchNorm  # noqa: F401
 from .vector_quantize import VectorQuantize  # noqa: F401
 from . import packing  # noqa: F401
 from . import progressive  # noqa: F401
-from .progressive import frame_cuts, image_clip  # noqa: F401
+from .progressive import frame_cuts, image_clip, model_decode_prefixes  # noqa: F401
 from . import shards  # noqa: F401
 
 __all__ = ["DCTAutoencoderFeatureExtractor", "DCTPatches", "PatchNorm", "LFQ", "VectorQuantize", "to_dict", "from_dict",
@@ -25,4 +25,4 @@ __all__ = ["DCTAutoencoderFeatureExtractor", "DCTPatches", "PatchNorm", "LFQ", "
            "GroupPatchesState", "build_attn_mask", "load_library", "DCTAEError", "DCTAEUnavailable",
            "LFQDistance", "compute_entropy_loss", "masked_mean", "calculate_perplexity",
            "reconstruction_losses", "masked_perplexity", "step_losses", "pixel_loss", "progressive", "frame_cuts",
-           "image_clip"]
+           "image_clip", "model_decode_prefixes"]

@@ -143,6 +143,12 @@ _SIGS = {
                              C.c_int32, _P], C.c_int),
     "dctae_image_clip": ([_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P, C.POINTER(C.c_int64), _P,
                           C.c_int32, _P], C.c_int),
+    # include/dctae_model_prefix.h: variable-length attention, the prefix token gather
+    "dctae_model_attention_varlen": ([_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P],
+                                     C.c_int),
+    "dctae_prefix_tokens": ([_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32,
+                             C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                             _P, _P, _P, _P], C.c_int),
     "dctae_dct2": ([_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P], C.c_int),
     "dctae_patch_spectrum": ([_P, C.POINTER(FECfg), _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P],
                              C.c_int),

@@ -115,6 +115,26 @@ void launch_adamw_pack(const dctae_optim_seg* segs, int count, int64_t n_work, c
 
 void launch_linear(const LinearArgs& a, int epi, hipStream_t s);
 void launch_attention(const AttnArgs& a, hipStream_t s);
+// variable-length form (include/dctae_model_prefix.h): a.R, a.S, a.ids, a.key_pad and a.lse are not read
+void launch_attention_varlen(const AttnArgs& a, int n_seq, int max_len, const int64_t* seq_start, const int32_t* seq_len,
+                             hipStream_t s);
+// the prefix token gather (dctae_model_prefix.hip); the four frame tables are device arrays of n_frames entries
+struct PrefixGatherArgs {
+  const int64_t* ids;       // (R, S)
+  const uint8_t* key_pad;   // (R, S)
+  const int64_t* pos;       // (R, S, 2)
+  const int64_t* ch;        // (R, S)
+  const void* codes;        // (R, S, ncb) int64 or int16
+  const int32_t* frame_row;
+  const int64_t* frame_id;
+  const int32_t* frame_m;
+  const int64_t* frame_start;
+  int64_t* out_codes;       // (M, ncb)
+  int64_t* out_ch;          // (M)
+  int64_t* out_pos;         // (M, 2)
+  int32_t S, ncb, codes16;
+};
+void launch_prefix_tokens(const PrefixGatherArgs& a, int n_frames, hipStream_t s);
 void launch_layernorm(const LnArgs& a, hipStream_t s);
 void launch_pos_add(const PosArgs& a, hipStream_t s);
 void launch_to_bf16(const float* x, int64_t ldx, int64_t M, int K, int Kp, uint16_t* out, hipStream_t s);

@@ -14,6 +14,9 @@
 //                   "mask" is ADDED (+1.0 where id_i == id_j and key j is a
 //                   pad, FE:580-584 -> modeling:131-133), computed from the
 //                   row's image ids and key_pad_mask (no S x S tensor)
+//   k_attention_varlen  the same body (dctae_attention_body.h) on the sequences
+//                   of a flat token stream, start and length from a table, no
+//                   bias term (include/dctae_model_prefix.h)
 //   k_layernorm     one wave per token row, fp32 statistics, bf16 out
 //   k_ln_pos        embedding LayerNorm (eps 1e-4) + encoder position terms
 //   k_pos_add       decoder position terms (in place)
@@ -254,178 +257,27 @@ constexpr int AQ = 256, AK = 64, AD = 64, ASTR = 72, AVS = 96, ATH = 4 * AQ / 2;
 
 // LSE: the training variant also writes each (row, head, query)'s log-sum-exp
 // in log2 units, mrun + log2(lsum), for the backward (dctae_model_bwd.hip)
+// The body is dctae_attention_body.h, shared by the two kernels below.
 template <bool LSE>
 __global__ __launch_bounds__(ATH) void k_attention(AttnArgs a) {
-  __shared__ __attribute__((aligned(16))) uint16_t Ks[AK * ASTR];
-  __shared__ __attribute__((aligned(16))) uint16_t Vs[AK * AVS];   // row-major; read transposed (ds_read_b64_tr_b16)
-  __shared__ __attribute__((aligned(16))) int32_t kid[AK];   // key image id, or -1 for a non-pad key (no bias)
-  __shared__ __attribute__((aligned(16))) uint16_t Os[AQ * ASTR];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int S = a.S, D = a.heads * AD;
-  const int q0 = blockIdx.x * AQ, h = blockIdx.y, b = blockIdx.z;
-  const int64_t rowbase = (int64_t)b * S;
-  const int64_t ld = 3ll * D;
-  const uint16_t* qkv = a.qkv;
-  // this lane's query and its Q fragments (B operand: Q[q][d kk*16 + 8 (l/32) ..])
-  const int ql = q0 + wave * 32 + (lane & 31);
-  const int qc = min(ql, S - 1);
-  bf16x8 qf[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk)
-    qf[kk] = *reinterpret_cast<const bf16x8*>(qkv + (rowbase + qc) * ld + h * AD + kk * 16 + (lane >> 5) * 8);
-  const int32_t my_id = (int32_t)a.ids[rowbase + qc];
-  const float sc = a.scale * 1.4426950408889634f;   // logits in log2 units
-  const float bias2 = 1.4426950408889634f;           // +1.0 bias in log2 units
-  f32x16 o[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) o[t][v] = 0.0f;
-  float mrun = -INFINITY, lsum = 0.0f;
-  for (int k0 = 0; k0 < S; k0 += AK) {
-    __syncthreads();   // previous block's K / V reads done
-    // stage K and V rows: 64 keys x 64 d, 16 B per load (two per thread each)
-#pragma unroll
-    for (int j = 0; j < AK * 8 / ATH; ++j) {
-      const int idx = tid + ATH * j, key = idx >> 3, seg = idx & 7;
-      const int kg = min(k0 + key, S - 1);
-      const uint16_t* src = qkv + (rowbase + kg) * ld + h * AD + seg * 8;
-      const uint4 kv = *reinterpret_cast<const uint4*>(src + D);
-      const uint4 vv = *reinterpret_cast<const uint4*>(src + 2 * D);
-      *reinterpret_cast<uint4*>(Ks + key * ASTR + seg * 8) = kv;
-      *reinterpret_cast<uint4*>(Vs + key * AVS + seg * 8) = vv;
-    }
-    bool pad = false;
-    if (tid < AK) {
-      const int kg = k0 + tid;
-      pad = kg < S && a.key_pad[rowbase + kg];
-      kid[tid] = pad ? (int32_t)a.ids[rowbase + kg] : -1;
-    }
-    const bool any_pad = __syncthreads_or(pad);   // block-uniform: the +1 bias only ever hits pad keys
-    // S^T tiles
-    f32x16 st[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int v = 0; v < 16; ++v) st[t][v] = 0.0f;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (t * 32 + (lane & 31)) * ASTR + kk * 16 + (lane >> 5) * 8);
-        st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], st[t], 0, 0, 0);
-      }
-    }
-    // scale + bias, block max over the 64 keys of this query (lanes l and l ^ 32).
-    // Without pad keys in the block the logits stay unscaled (sce = sc) and the
-    // scale is applied inside the exponent's FMA; with pad keys they are scaled
-    // and biased here (sce = 1).
-    float bm = -INFINITY;
-    float sce = sc;
-    if (any_pad) {
-      sce = 1.0f;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const int4 ki = *reinterpret_cast<const int4*>(kid + t * 32 + 8 * q4 + 4 * (lane >> 5));
-          st[t][4 * q4 + 0] = st[t][4 * q4 + 0] * sc + (ki.x == my_id ? bias2 : 0.0f);
-          st[t][4 * q4 + 1] = st[t][4 * q4 + 1] * sc + (ki.y == my_id ? bias2 : 0.0f);
-          st[t][4 * q4 + 2] = st[t][4 * q4 + 2] * sc + (ki.z == my_id ? bias2 : 0.0f);
-          st[t][4 * q4 + 3] = st[t][4 * q4 + 3] * sc + (ki.w == my_id ? bias2 : 0.0f);
-        }
-    }
-    if (k0 + AK > S) {   // last, partial key block
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int v = 0; v < 16; ++v)
-          if (k0 + t * 32 + 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3) >= S) st[t][v] = -INFINITY;
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) bm = fmaxf(bm, st[t][v]);
-    {
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(bm), __float_as_uint(bm), false, false);
-      bm = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * sce;
-    }
-    // lazy rescale: the reference max moves only when the block max exceeds it
-    // by more than 8 (log2 units), so p = 2^(s - m) <= 2^8 stays exact in fp32
-    // and in range for bf16; O and the sum always share the same m, so the
-    // normalised result is unchanged.  The O rescale (AGPR round trip) runs
-    // only when some lane moved its max.
-    if (bm > mrun + 8.0f) {
-      const float alpha = __builtin_amdgcn_exp2f(mrun - bm);   // 0 on the first block (mrun = -inf)
-      mrun = bm;
-      lsum *= alpha;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int v = 0; v < 16; ++v) o[t][v] *= alpha;
-    }
-    const float nm = -mrun;
-    // P (bf16) in B-operand order: key step kk = (tile kk / 2, quarters 2 (kk % 2), +1)
-    bf16x8 pf[4];
-    float ls2[2] = {0.0f, 0.0f};   // two partial sums (pairs for packed adds)
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const int t = kk >> 1, v0 = 8 * (kk & 1);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        // raw v_exp_f32: exp2f's denormal-range fix-up (5 VALU ops per call)
-        // is not needed (results below 2^-126 are negligible probabilities)
-        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[t][v0 + e], sce, nm));
-        ls2[e & 1] += p;
-        pf[kk][e] = (__bf16)p;
-      }
-    }
-    lsum += ls2[0] + ls2[1];
-    // O^T += V^T P^T; the A fragment V^T[d = 32 dt + lane % 32][keys kb + (0..3), kb + 8 + (0..3)] comes
-    // from the row-major V tile by two transposed reads: lane 4q + p of each 16-lane group addresses key
-    // row kb + q, columns 4p .. 4p + 3 of the group's 16 d columns, and receives its own column
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    const int gq = (lane & 15) >> 2, gp = lane & 3, gx = (lane >> 4) & 1;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const int kb = 32 * (kk >> 1) + 8 * (2 * (kk & 1)) + 4 * (lane >> 5);
-        const uint16_t* vr = Vs + (kb + gq) * AVS + 32 * dt + 16 * gx + 4 * gp;
-        const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)vr);
-        const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(vr + 8 * AVS));
-        bf16x8 vf;
-        short* vsh = reinterpret_cast<short*>(&vf);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          vsh[e] = lo[e];
-          vsh[4 + e] = hi[e];
-        }
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[kk], o[dt], 0, 0, 0);
-      }
-  }
-  // normalise: the query's sum is split over lanes l and l ^ 32
-  {
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lsum), __float_as_uint(lsum), false, false);
-    lsum = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-  }
-  const float inv = 1.0f / lsum;
-  if (LSE && lane < 32 && ql < S) a.lse[((int64_t)b * a.heads + h) * S + ql] = mrun + __log2f(lsum);
-  // O^T[d = 32 dt + 8 (v/4) + 4 (l/32) + v%4][query l%32] -> Os[query][d] -> coalesced rows
-  const int qr = wave * 32 + (lane & 31);
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int d = 32 * dt + 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3);
-      Os[qr * ASTR + d] = f2bf(o[dt][v] * inv);
-    }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < AQ * 8 / ATH; ++j) {
-    const int idx = tid + ATH * j, r = idx >> 3, seg = idx & 7;
-    if (q0 + r < S)
-      *reinterpret_cast<uint4*>(a.out + (rowbase + q0 + r) * (int64_t)a.ldo + h * AD + seg * 8) =
-          *reinterpret_cast<const uint4*>(Os + r * ASTR + seg * 8);
-  }
+  constexpr bool VARLEN = false;
+  constexpr const int64_t* seq_start = nullptr;
+  constexpr const int32_t* seq_len = nullptr;
+#include "dctae_attention_body.h"
+}
+
+// sequence blockIdx.z of the table; a query block at or beyond the sequence's
+// length (every block of an empty sequence) leaves before the first barrier
+__global__ __launch_bounds__(ATH) void k_attention_varlen(AttnArgs a, const int64_t* seq_start, const int32_t* seq_len) {
+  constexpr bool LSE = false, VARLEN = true;
+#include "dctae_attention_body.h"
+}
+
+void launch_attention_varlen(const AttnArgs& a, int n_seq, int max_len, const int64_t* seq_start, const int32_t* seq_len,
+                             hipStream_t s) {
+  if (n_seq <= 0 || max_len <= 0) return;
+  const dim3 grid((max_len + AQ - 1) / AQ, a.heads, n_seq);
+  hipLaunchKernelGGL(k_attention_varlen, grid, dim3(ATH), 0, s, a, seq_start, seq_len);
 }
 
 void launch_attention(const AttnArgs& a, hipStream_t s) {

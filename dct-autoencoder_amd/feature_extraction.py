@@ -635,6 +635,14 @@ class DCTAutoencoderFeatureExtractor:
         from . import progressive
         return progressive.decode_prefixes(self, dct_patches, codes, patchnorm, lfq, prefixes, output_dtype, clip)
 
+    def model_decode_prefixes(self, model, dct_patches: DCTPatches, codes: torch.Tensor, prefixes,
+                              output_dtype: torch.dtype = torch.float32, clip=None) -> List[List[torch.Tensor]]:
+        """The prefix frames through the transformer decoder (progressive.model_decode_prefixes): frame (i, k)
+        is, bit for bit, ``postprocess`` of ``model.decode_from_codes`` on the first min(k, n_i) real tokens of
+        image i as a one-row batch without padding (decode_gif.py), all frames in one pass per chunk."""
+        from . import progressive
+        return progressive.model_decode_prefixes(self, model, dct_patches, codes, prefixes, output_dtype, clip)
+
     def image_clip(self, images: Sequence[torch.Tensor], output_dtype: torch.dtype = torch.float32
                    ) -> List[torch.Tensor]:
         """util.py:143-147 on a list of (3, H, W) fp32 device images of any sizes, in one launch sequence

@@ -207,6 +207,54 @@ class _Packed:
         self.b[name] = b.detach().float().contiguous() if b is not None else None
 
 
+class SeqTable:
+    """The sequences of a flat token stream of ``n_rows`` rows for the
+    variable-length attention (include/dctae_model_prefix.h): sequence ``j`` is
+    the rows ``[starts[j], starts[j] + lens[j])``.  Built from host lists and
+    checked there, since the library call cannot read the device tables: a
+    negative start or length, a sequence beyond ``n_rows``, two sequences that
+    overlap, or ``max_len`` (default: the longest) below some length is a
+    ValueError."""
+
+    def __init__(self, starts, lens, n_rows: int, device, max_len: Optional[int] = None):
+        starts, lens = [int(v) for v in starts], [int(v) for v in lens]
+        if len(starts) != len(lens):
+            raise ValueError(f"SeqTable: {len(starts)} starts for {len(lens)} lengths")
+        if len(starts) > 65535:
+            raise ValueError(f"SeqTable: at most 65535 sequences per call, got {len(starts)}")
+        longest = max(lens, default=0)
+        self.max_len = longest if max_len is None else int(max_len)
+        if self.max_len < longest:
+            raise ValueError(f"SeqTable: max_len = {self.max_len} is below the longest sequence ({longest})")
+        end = 0
+        for s, n in sorted(zip(starts, lens)):
+            if s < 0 or n < 0 or s + n > n_rows:
+                raise ValueError(f"SeqTable: sequence [{s}, {s + n}) outside the {n_rows} rows of the stream")
+            if n and s < end:
+                raise ValueError(f"SeqTable: the sequence at row {s} overlaps the one before it")
+            end = max(end, s + n)
+        self.n_seq, self.n_rows = len(starts), int(n_rows)
+        self.start = torch.tensor(starts, dtype=torch.int64, device=device)
+        self.len = torch.tensor(lens, dtype=torch.int32, device=device)
+
+
+def attention_varlen(qkv: torch.Tensor, seqs: SeqTable, heads: int, out: torch.Tensor) -> torch.Tensor:
+    """dctae_model_attention_varlen: full softmax attention inside each sequence
+    of ``seqs`` on ``qkv`` (M, 3 * 64 * heads) bf16 bits (int16), into the rows
+    of ``out`` (M, >= 64 * heads) bf16 bits that belong to a sequence; every
+    other row of ``out`` is left as it is."""
+    if qkv.dim() != 2 or qkv.shape[0] != seqs.n_rows or out.shape[0] != seqs.n_rows or qkv.shape[1] != 192 * heads:
+        raise ValueError(f"attention_varlen: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} for {seqs.n_rows} rows, "
+                         f"{heads} heads")
+    if qkv.device != seqs.start.device or out.device != qkv.device:
+        raise RuntimeError("attention_varlen: qkv, out and the sequence table must be on one device")
+    ctx = _lib.context(qkv.device)
+    ctx.check(ctx.lib.dctae_model_attention_varlen(ctx.h, seqs.n_seq, seqs.max_len, heads, 64, _lib.ptr(qkv),
+                                                   _lib.ptr(seqs.start), _lib.ptr(seqs.len), _lib.ptr(out),
+                                                   out.stride(0), _lib.stream_ptr(qkv.device)), "self_attn_varlen")
+    return out
+
+
 class DCTAutoencoder(nn.Module):
     def __init__(self, config: DCTAutoencoderConfig):
         super().__init__()
@@ -369,9 +417,10 @@ class DCTAutoencoder(nn.Module):
                                                 _lib.stream_ptr(h.device)), "layer_norm")
         return out
 
-    def _clip(self, side: str, h: torch.Tensor, dp: DCTPatches):
+    def _clip(self, side: str, h: torch.Tensor, dp: DCTPatches, seqs: Optional[SeqTable] = None):
         """CLIPEncoder.forward (transformers 4.35.2 CLIPEncoderLayer) on the f32
-        residual stream h (M, D), in place."""
+        residual stream h (M, D), in place.  ``seqs``: attention inside the
+        sequences of that table instead of the padded rows of ``dp``."""
         ctx = self._ctx(h)
         pk = self._weights()
         enc = getattr(self, side)
@@ -389,8 +438,11 @@ class DCTAutoencoder(nn.Module):
         for i, L in enumerate(enc.layers):
             self._layernorm(ctx, h, L.layer_norm1, a)
             self._linear(ctx, a, pk.w[f"{side}.{i}.qkv"], pk.b[f"{side}.{i}.qkv"], 3 * d, LIN_BF16, qkv)
-            ctx.check(ctx.lib.dctae_model_attention(ctx.h, r, s, c.num_attention_heads, 64, _lib.ptr(qkv),
-                                                    _lib.ptr(ids), _lib.ptr(kp), _lib.ptr(o), d, st), "self_attn")
+            if seqs is not None:
+                attention_varlen(qkv, seqs, c.num_attention_heads, o)
+            else:
+                ctx.check(ctx.lib.dctae_model_attention(ctx.h, r, s, c.num_attention_heads, 64, _lib.ptr(qkv),
+                                                        _lib.ptr(ids), _lib.ptr(kp), _lib.ptr(o), d, st), "self_attn")
             self._linear(ctx, o, pk.w[f"{side}.{i}.out"], pk.b[f"{side}.{i}.out"], d, LIN_F32_RESIDUAL, h)
             self._layernorm(ctx, h, L.layer_norm2, a)
             self._linear(ctx, a, pk.w[f"{side}.{i}.fc1"], pk.b[f"{side}.{i}.fc1"], c.intermediate_size,
@@ -505,7 +557,7 @@ class DCTAutoencoder(nn.Module):
         return self._decode_from_codes_eval(codes, do_inv_norm, **dct_patches_kwargs)
 
     @torch.no_grad()
-    def _decode_from_codes_eval(self, codes, do_inv_norm=False, **dct_patches_kwargs) -> DCTPatches:
+    def _decode_from_codes_eval(self, codes, do_inv_norm=False, _seqs=None, **dct_patches_kwargs) -> DCTPatches:
         vq = self.vq_model
         q = vq.indices_to_codes(codes, project_out=False)
         if vq.has_projections:
@@ -517,7 +569,107 @@ class DCTAutoencoder(nn.Module):
             q = self._linear(ctx, qb, pk.w["proj_out_vq"], pk.b["proj_out_vq"], vq.dim, LIN_F32,
                              torch.empty(qm.shape[0], vq.dim, device=qm.device)).view(*lead, vq.dim)
         x = DCTPatches(patches=q, **dct_patches_kwargs)
+        if _seqs is not None:
+            return self._decode_eval(x, do_inv_norm, _seqs)
         return self.decode(x, do_inv_norm=do_inv_norm)
+
+    def decode_prefixes(self, dct_patches: DCTPatches, codes: torch.Tensor, prefixes, do_inv_norm: bool = True):
+        """The model prefix frames of a packed batch (progressive.py's module
+        docstring) through the decoder in one pass per chunk: frame
+        ``(i, k)`` is ``decode_from_codes`` of the first ``min(k, n_i)`` real
+        tokens of image ``i`` as a one-row batch without padding, bit for bit.
+        ``.eval()`` only, under ``no_grad``.  ``prefixes``: ints for every image,
+        or one sequence per image.  ``codes``: int64 or int16.
+
+        Returns ``(frames, which)``: ``frames`` a DCTPatches in the ordinary
+        packed format whose images are, in order, the frames with
+        ``min(k, n_i) >= 1`` (one row per chunk of at most
+        ``progressive.PREFIX_TOKENS_PER_CALL`` tokens, a frame's id its number
+        in the row, rows padded at the end to the longest; None without such a
+        frame), ``which`` their ``(image, k)``.  Frames with
+        ``min(k, n_i) == 0`` decode nothing through the model and are left out
+        (``progressive.model_decode_prefixes`` builds them).  Reading
+        ``batched_image_ids`` / ``key_pad_mask`` on the host is the call's one
+        host synchronisation."""
+        dp, which, _, _ = self._decode_prefixes(dct_patches, codes, prefixes, do_inv_norm)
+        return dp, which
+
+    @torch.no_grad()
+    def _decode_prefixes(self, dct_patches: DCTPatches, codes: torch.Tensor, prefixes, do_inv_norm: bool = True):
+        from . import _ops, progressive
+        if self.training:
+            raise NotImplementedError("decode_prefixes runs in .eval() only (no gradients through frames)")
+        vq = self.vq_model
+        if not isinstance(codes, torch.Tensor):
+            raise TypeError(f"decode_prefixes codes: a tensor expected, got {type(codes)}")
+        _ops.codes_dtype_suffix(codes.dtype, "decode_prefixes codes")
+        if codes.dtype == torch.int16:
+            _ops.check_codes16(vq.cfg(), "decode_prefixes")
+        progressive._split_prefixes(prefixes)   # a negative prefix is refused before anything is read
+        ids, kp = dct_patches.batched_image_ids, dct_patches.key_pad_mask
+        dev = codes.device
+        for n, p in self.named_parameters():
+            if p.device != dev:
+                raise RuntimeError(f"parameter {n} is on {p.device}, the codes on {dev}: move the model with .to()")
+        for name, v in (("batched_image_ids", ids), ("key_pad_mask", kp), ("patch_channels", dct_patches.patch_channels),
+                        ("patch_positions", dct_patches.patch_positions)):
+            if v.device != dev:
+                raise RuntimeError(f"{name} is on {v.device}, the codes on {dev}")
+        r, s = kp.shape
+        if codes.dim() != 3 or tuple(codes.shape[:2]) != (r, s) or codes.shape[2] != vq.num_codebooks:
+            raise ValueError(f"decode_prefixes codes: ({r}, {s}, {vq.num_codebooks}) expected, got {tuple(codes.shape)}")
+        plan = progressive.model_frames(ids.cpu(), kp.cpu(), prefixes)   # the one host read
+        live = [f for f in range(len(plan.m)) if plan.m[f] > 0]
+        which = [(plan.img[f], plan.k[f]) for f in live]
+        if not live:
+            return None, which, plan, []
+        ctx = self._ctx(codes)
+        st = _lib.stream_ptr(dev)
+        ncb = vq.num_codebooks
+        ids_d, kp_d = ids.long().contiguous(), kp.to(torch.uint8).contiguous()
+        ch_d, pos_d = self._ch_pos(dct_patches)
+        cc = codes.contiguous()
+        ctype = _lib.CODES_I16 if cc.dtype == torch.int16 else _lib.CODES_I64
+        ms = [plan.m[f] for f in live]
+        chunks = progressive.model_frame_chunks(ms, progressive.PREFIX_TOKENS_PER_CALL)
+        width = max(sum(ms[b:e]) for b, e in chunks)
+        pd = self.proj_out[1].weight.shape[0]
+        out = DCTPatches(patches=torch.zeros(len(chunks), width, pd, device=dev),
+                         key_pad_mask=torch.ones(len(chunks), width, dtype=torch.bool, device=dev),
+                         batched_image_ids=torch.zeros(len(chunks), width, dtype=torch.long, device=dev),
+                         patch_channels=torch.zeros(len(chunks), width, dtype=torch.long, device=dev),
+                         patch_positions=torch.zeros(len(chunks), width, 2, dtype=torch.long, device=dev),
+                         patch_sizes=[dct_patches.patch_sizes[plan.img[f]] for f in live],
+                         original_sizes=[dct_patches.original_sizes[plan.img[f]] for f in live])
+        layout = []   # (row, first slot, tokens) of every frame in the frames batch
+        for c, (b, e) in enumerate(chunks):
+            lens = ms[b:e]
+            starts = [sum(lens[:j]) for j in range(len(lens))]
+            layout += [(c, s0, n) for s0, n in zip(starts, lens)]
+            m = sum(lens)
+            fr = [live[j] for j in range(b, e)]
+            g_codes = torch.empty(m, ncb, dtype=torch.long, device=dev)
+            g_ch = torch.empty(m, dtype=torch.long, device=dev)
+            g_pos = torch.empty(m, 2, dtype=torch.long, device=dev)
+            keep = (_lib.i32([plan.row[f] for f in fr]), _lib.i64([plan.lid[f] for f in fr]), _lib.i32(lens),
+                    _lib.i64(starts))
+            ctx.check(ctx.lib.dctae_prefix_tokens(
+                ctx.h, r, s, _lib.ptr(ids_d), _lib.ptr(kp_d), _lib.ptr(pos_d), _lib.ptr(ch_d), _lib.ptr(cc), ctype, ncb,
+                len(fr), C.cast(keep[0], C.POINTER(C.c_int32)), C.cast(keep[1], C.POINTER(C.c_int64)),
+                C.cast(keep[2], C.POINTER(C.c_int32)), C.cast(keep[3], C.POINTER(C.c_int64)), _lib.ptr(g_codes),
+                _lib.ptr(g_ch), _lib.ptr(g_pos), st), "dctae_prefix_tokens")
+            seqs = SeqTable(starts, lens, m, dev)
+            fid = torch.repeat_interleave(torch.arange(len(lens)), torch.tensor(lens)).to(dev).view(1, m)
+            x = self._decode_from_codes_eval(
+                g_codes.view(1, m, ncb), do_inv_norm, _seqs=seqs, key_pad_mask=torch.zeros(1, m, dtype=torch.bool, device=dev),
+                batched_image_ids=fid, patch_channels=g_ch.view(1, m), patch_positions=g_pos.view(1, m, 2),
+                patch_sizes=out.patch_sizes[b:e], original_sizes=out.original_sizes[b:e])
+            out.patches[c, :m] = x.patches[0]
+            out.key_pad_mask[c, :m] = False
+            out.batched_image_ids[c, :m] = fid[0]
+            out.patch_channels[c, :m] = g_ch
+            out.patch_positions[c, :m] = g_pos
+        return out, which, plan, layout
 
     def decode(self, x: DCTPatches, do_inv_norm: bool = False) -> DCTPatches:
         if self.training:
@@ -539,7 +691,7 @@ class DCTAutoencoder(nn.Module):
         return x
 
     @torch.no_grad()
-    def _decode_eval(self, x: DCTPatches, do_inv_norm: bool = False) -> DCTPatches:
+    def _decode_eval(self, x: DCTPatches, do_inv_norm: bool = False, seqs: Optional[SeqTable] = None) -> DCTPatches:
         self._check_mode(x)
         pk = self._weights()
         r, s, d = x.patches.shape
@@ -547,7 +699,7 @@ class DCTAutoencoder(nn.Module):
         ctx = self._ctx(x.patches)
         x = self.add_pos_embedding_decoder_(x)
         h = x.patches.view(r * s, d)
-        self._clip("decoder", h, x)
+        self._clip("decoder", h, x, seqs)
         a = self._layernorm(ctx, h, self.proj_out[0], torch.empty(r * s, d, dtype=torch.int16, device=dev))
         pd = self.proj_out[1].weight.shape[0]
         y = self._linear(ctx, a, pk.w["proj_out"], None, pd, LIN_F32, torch.empty(r * s, pd, device=dev))

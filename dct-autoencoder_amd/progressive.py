@@ -21,12 +21,38 @@ tokens at one place inside the prefix the later slot wins.
 ``prefixes`` is one sequence of ints applied to every image, or one sequence
 per image; the result is a list per image of that image's frames, in the order
 of its prefixes.
+
+Through the transformer (include/dctae_model_prefix.h).  The frames
+above cut the token stream in front of the feature extractor's decode; the
+reference's decode_gif.py cuts it in front of the trained decoder:
+``autoenc.decode_from_codes(codes[:, :i], ...)`` on a one-image row, then
+``proc.postprocess``.  The MODEL PREFIX FRAME ``(i, k)``, ``k >= 0``, with
+``m = min(k, n_i)``:
+
+  * ``m >= 1``: take the first ``m`` real tokens of image ``i`` (interior padded
+    slots skipped), place them as a one-row batch of length ``m`` with
+    ``key_pad_mask`` all False and ``batched_image_ids`` all 0, run
+    ``model.decode_from_codes(codes_row, do_inv_norm=True, **that_row)`` in
+    ``.eval()``, then ``fe.postprocess``.  The frame equals that result bit for
+    bit (decode_gif.py:60-77 on its one-image row).
+  * ``m == 0``: the decode of an empty spectrum, bit for bit what
+    ``fe.postprocess_prefixes(dp, [0])`` returns for image ``i``.
+
+So a frame does not depend on which other images or how much padding share the
+row, and the ``k >= n_i`` frame is the image decoded alone in an unpadded row.
+That is in general NOT image ``i`` of ``model.decode_from_codes`` on the packed
+batch: there the row's other images and its pad keys take part in every
+softmax, because the reference's boolean ``attn_mask`` is added to the logits
+and masks nothing.  For the same reason a frame is a truncated row, not a
+masked one.  ``model_decode_prefixes`` batches the frames without padding: every
+linear, LayerNorm and position kernel is token-wise, and the attention kernel
+reads its row's first token and length from a table.
 """
 from __future__ import annotations
 
 import ctypes as C
 import numbers
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -41,6 +67,11 @@ from ._lib import Frames, i32, i64, ptr
 # depend on the cut.
 FRAME_SCRATCH_BYTES = 1 << 30
 MAX_FRAMES_PER_CALL = 65535   # the library's bound on n_frames
+# The model prefix frames of one pass through the decoder hold at most this many
+# tokens together (one frame at least): the frame list is cut into chunks of
+# consecutive frames.  Every kernel but attention is token-wise and attention
+# stays inside a frame, so a frame's values do not depend on the cut.
+PREFIX_TOKENS_PER_CALL = 32768
 
 
 def _check_clip(clip) -> int:
@@ -336,3 +367,112 @@ def decode_prefixes(fe, dct_patches, codes: torch.Tensor, patchnorm, lfq, prefix
         dp.patches = patchnorm.inverse_norm(dp)
         return postprocess_prefixes(fe, dp, prefixes, output_dtype, clip)
     return decode_frames(*args(), codes=codes, norm=patchnorm.state(), lfq=lfq.cfg())
+
+
+# ---- model prefix frames (through the transformer decoder) -----------------------------------
+class ModelFrames(NamedTuple):
+    """the frames of ``prefixes``, image by image and within an image in prefix
+    order: frame ``f`` is image ``img[f]`` at prefix ``k[f]``, the first ``m[f]``
+    real tokens of id ``lid[f]`` in row ``row[f]``; ``n_img`` images in the batch"""
+    img: List[int]
+    k: List[int]
+    row: List[int]
+    lid: List[int]
+    m: List[int]
+    n_img: int
+
+
+def model_frames(ids: torch.Tensor, key_pad: torch.Tensor, prefixes) -> ModelFrames:
+    """The model prefix frames of ``prefixes`` on the batch (``ids`` (R, S)
+    integer, ``key_pad`` (R, S) bool, CPU tensors), ``m = min(k, n_i)`` each
+    (0: the frame goes round the model).  A pure host function."""
+    ids = torch.as_tensor(ids).long()
+    key_pad = torch.as_tensor(key_pad).to(torch.bool)
+    if ids.is_cuda or key_pad.is_cuda:
+        raise TypeError("model_frames works on CPU tensors: pass ids.cpu() / key_pad.cpu()")
+    if ids.dim() != 2 or ids.shape != key_pad.shape:
+        raise ValueError(f"ids {tuple(ids.shape)} and key_pad {tuple(key_pad.shape)} must be (R, S) both")
+    places = _places(ids)
+    per = per_image_prefixes(prefixes, len(places))
+    out = ModelFrames([], [], [], [], [], len(places))
+    for i, (r, lid) in enumerate(places):
+        if not per[i]:
+            continue
+        n = int(((ids[r] == lid) & ~key_pad[r]).sum())
+        for k in per[i]:
+            out.img.append(i)
+            out.k.append(k)
+            out.row.append(r)
+            out.lid.append(lid)
+            out.m.append(min(k, n))
+    return out
+
+
+def model_frame_chunks(ms: Sequence[int], budget: Optional[int] = None) -> List[Tuple[int, int]]:
+    """[begin, end) runs of consecutive frames of ``ms`` tokens each whose token
+    total stays within ``budget`` (default PREFIX_TOKENS_PER_CALL), one frame at
+    least per run (a frame longer than the budget is a run of its own)"""
+    return _chunks(list(ms), PREFIX_TOKENS_PER_CALL if budget is None else budget)
+
+
+def _fft_sized(fe, size) -> bool:
+    """the images whose one-image batch the decode sends down its 512 x 512 path (dctae_frames.h)"""
+    return tuple(int(v) for v in size) == (512, 512) and fe.patch_size == 14
+
+
+@torch.no_grad()
+def model_decode_prefixes(fe, model, dct_patches, codes: torch.Tensor, prefixes,
+                          output_dtype: torch.dtype = torch.float32, clip=None) -> List[List[torch.Tensor]]:
+    """The model prefix frames of a packed batch (module docstring): per image
+    the list of its (3, H, W) frames of ``output_dtype`` in prefix order, the
+    decoder run once per chunk of frames (``model.decode_prefixes``) and the
+    frames batch passed through ``fe.postprocess`` (overridden stage hooks
+    included); ``clip="minmax"``: every frame through ``image_clip``, bytes
+    from the clipped fp32 value.  Frames with ``min(k, n_i) == 0`` come from
+    ``postprocess_prefixes`` at prefix 0."""
+    _pixel_tag(output_dtype, "model_decode_prefixes output_dtype")
+    _check_clip(clip)
+    dp, which, plan, layout = model._decode_prefixes(dct_patches, codes, prefixes, do_inv_norm=True)
+    post_dtype = torch.float32 if clip is not None else output_dtype
+    live: List[torch.Tensor] = []
+    if dp is not None:
+        # the decode picks its path from the whole batch it is given: the frames of images that a one-image
+        # batch sends down the 512 x 512 path are kept apart from the others, run by run within a row
+        kind = [(row, _fft_sized(fe, dp.original_sizes[f])) for f, (row, _, _) in enumerate(layout)]
+        b = 0
+        while b < len(layout):
+            e = b + 1
+            while e < len(layout) and kind[e] == kind[b]:
+                e += 1
+            row, lo, hi = layout[b][0], layout[b][1], layout[e - 1][1] + layout[e - 1][2]
+            sub = dp.shallow_copy()
+            sub.attn_mask = None
+            sub.patches = dp.patches[row:row + 1, lo:hi].contiguous()
+            sub.key_pad_mask = dp.key_pad_mask[row:row + 1, lo:hi].contiguous()
+            sub.batched_image_ids = (dp.batched_image_ids[row:row + 1, lo:hi] - dp.batched_image_ids[row, lo]).contiguous()
+            sub.patch_channels = dp.patch_channels[row:row + 1, lo:hi].contiguous()
+            sub.patch_positions = dp.patch_positions[row:row + 1, lo:hi].contiguous()
+            sub.patch_sizes, sub.original_sizes = dp.patch_sizes[b:e], dp.original_sizes[b:e]
+            live += fe._postprocess_no_grad(sub, post_dtype)
+            b = e
+        if clip is not None:
+            live = _clip_images([im.float() for im in live], output_dtype)
+    # the frames that hold no token: the k = 0 frames of the batch as it is (no patch value is read)
+    zero_of = {}
+    need = sorted({i for i, m in zip(plan.img, plan.m) if m == 0})
+    if need:
+        dp0 = dct_patches.shallow_copy()
+        r, s = dct_patches.key_pad_mask.shape
+        dp0.patches = torch.zeros(r, s, fe.patch_size ** 2, device=dct_patches.key_pad_mask.device)
+        z = postprocess_prefixes(fe, dp0, [[0] if i in need else [] for i in range(plan.n_img)], output_dtype, clip)
+        zero_of = {i: z[i][0] for i in need}
+    res: List[List[torch.Tensor]] = [[] for _ in range(plan.n_img)]
+    it = iter(live)
+    used = set()
+    for i, m in zip(plan.img, plan.m):
+        if m > 0:
+            res[i].append(next(it))
+        else:
+            res[i].append(zero_of[i].clone() if i in used else zero_of[i])
+            used.add(i)
+    return res
