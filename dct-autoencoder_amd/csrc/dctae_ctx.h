@@ -6,7 +6,9 @@
 //   dctae_plan.hip     DCT matrices, GEMM problems and tile lists, FFT / Bluestein plans
 //   dctae_encode.hip   the encode plan and launch sequence
 //   dctae_enc_layout.h the encode plan's routes, workspace regions, chunk cut and staging carve (no HIP calls)
-//   dctae_decode.hip   the decode family's planner (DecodeBatch, below) and the decode launch sequences
+//   dctae_decode.hip   the decode family's planner (DecodeBatch, below) and the one decode launch sequence
+//   dctae_dec_layout.h the decode family's path choice and workspace layouts, forward and backward (no HIP calls)
+//   dctae_frames.hip   the frame kernels and image_clip; dctae_decode_frames plans through decode_impl
 //   dctae_decode_bwd.hip  the decode's backward and the pixel loss (kernels and launch sequence)
 //   dctae_api_ops.hip  PatchNorm, LFQ, VectorQuantize and transformer entry points
 #pragma once
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "../../include/dctae.h"
+#include "../../include/dctae_frames.h"
 #include "dctae_internal.h"
 #include "dctae_launch.h"
 #include "dctae_options.h"
@@ -260,8 +263,8 @@ int fft_plan_for(dctae_ctx* ctx, int N, int P, FftPlan* out);
 inline int bs_lidx(int L) { return L == 256 ? 0 : L == 512 ? 1 : L == 1024 ? 2 : 3; }
 constexpr int kBsL[4] = {256, 512, 1024, 2048};
 
-// ---- dctae_decode.hip: what dctae_decode, dctae_decode_normed and dctae_decode_backward share ----
-// the packed batch as the three entry points take it (include/dctae.h)
+// ---- dctae_decode.hip: what the decodes, dctae_decode_frames and dctae_decode_backward share ----
+// the packed batch as the entry points take it (include/dctae.h)
 struct DecodeBatch {
   const dctae_fe_cfg* cfg;
   int32_t n_rows;
@@ -275,6 +278,12 @@ struct DecodeBatch {
   const int64_t *pos, *ch;
   hipStream_t s;
 };
+inline DecodeBatch decode_batch(const dctae_fe_cfg* cfg, int32_t n_rows, const int32_t* img_lut, int32_t lut_w,
+                                int32_t n_img, const int32_t* out_hw, const int64_t* out_off, const int32_t* patch_hw,
+                                const int64_t* ids, const uint8_t* key_pad, const int64_t* pos, const int64_t* ch,
+                                void* stream) {
+  return {cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch, (hipStream_t)stream};
+}
 int decode_check(dctae_ctx* ctx, const DecodeBatch& B, const char* own, bool img_bufs, bool tok_bufs);
 int decode_geometry(dctae_ctx* ctx, const DecodeBatch& B, std::vector<ImgDesc>& D, int64_t* max_hw);
 int decode_gemm_pair(dctae_ctx* ctx, const dctae_fe_cfg* cfg, const ImgDesc& d, float* ws, GemmProblem* g1,
@@ -292,6 +301,17 @@ struct CodeSrc {
 int check_codes16(dctae_ctx* ctx, const dctae_lfq* lfq);
 DecodeArgs decode_args(const dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* norm, const dctae_lfq* lfq,
                        const void* codes, const float* patches, const int32_t* lut, bool normed);
+// the call body of every decode entry.  fr = NULL: the batch's images into out at B.out_off; else the frames of
+// fr into out at fr->out_off (B.out_off unused), with clip the image_clip of each
+int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* norm, const dctae_lfq* lfq,
+                const CodeSrc& codes, const float* patches, void* out, PixelType px, bool normed,
+                const dctae_frames* fr = nullptr, bool clip = false);
+
+// ---- dctae_frames.hip ----
+int frames_check(dctae_ctx* ctx, const DecodeBatch& B, const dctae_frames* fr);
+// descs / mm on the device; two timed stages: clip_minmax, clip_store
+int clip_launch(dctae_ctx* ctx, const ClipSpan* descs, int n, int64_t max_n, const float* in, uint32_t* mm, void* out,
+                PixelType px, hipStream_t s);
 
 // ---- dctae_encode.hip ----
 void drop_encode_plan(dctae_ctx* ctx);   // dctae_ctx_destroy: EncPlan is complete only there

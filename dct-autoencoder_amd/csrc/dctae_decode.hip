@@ -1,7 +1,9 @@
 // The decode engine: dctae_decode and dctae_decode_normed, and their byte-output
 // forms dctae_decode_u8 and dctae_decode_normed_u8 (include/dctae_u8_out.h), and
 // the int16-code forms dctae_decode_c16 and dctae_decode_u8_c16 (include/dctae_codes16.h).
+// dctae_decode_frames (dctae_frames.hip) plans and launches through the same decode_impl.
 #include "dctae_ctx.h"
+#include "dctae_dec_layout.h"
 #include "../../include/dctae_u8_out.h"
 #include "../../include/dctae_codes16.h"
 
@@ -113,85 +115,23 @@ int check_codes16(dctae_ctx* ctx, const dctae_lfq* lfq) {
   return 0;
 }
 
-}  // namespace dctae
-
-// decode of 512 x 512 images on the FFT path: token map -> column DCT-III
-// (tokens expanded in the kernel) -> U -> row DCT-III + IPT -> RGB.
-// rgb / px: the caller's images and their pixel type (ImgDesc::rgb_off in pixels)
-static int decode_fft(OrderedCall& oc, const DecodeBatch& B, std::vector<ImgDesc>& D, const FftPlan& fpl,
-                      const dctae_norm* norm, const dctae_lfq* lfq, const CodeSrc& codes, const float* patches,
-                      void* rgb, PixelType px, bool normed) {
-  dctae_ctx* ctx = oc.ctx;
-  const hipStream_t s = oc.s;
-  const dctae_fe_cfg* cfg = B.cfg;
-  const int n_img = B.n_img;
-  // 32 kept tile columns on the default row kernel: U in the band layout
-  // (k_idct_cols512b); otherwise row-major U (k_idct_cols512)
-  const bool rows512 = ctx->opt.dec_rows_kernel == 3 && D[0].qw == 32;
-  const bool band = rows512 && ctx->opt.dec_cols_kernel == 2;
-  // k_idct_rows512 stores four byte pixels at once (dctae_u8_out.h): refused before any launch
-  for (int i = 0; px == PixelType::kU8 && rows512 && i < n_img; ++i)
-    if (((uintptr_t)rgb + (uintptr_t)D[i].rgb_off) % 4)
-      return fail(ctx, DCTAE_EINVAL, "image " + std::to_string(i) + ": a 512 x 512 byte image on the 512-wide row "
-                  "kernel must start 4-byte aligned (rgb_dev + out_off[i])");
-  int64_t wsf = 0;
-  std::vector<int2> rb;
-  for (int i = 0; i < n_img; ++i) {
-    ImgDesc& d = D[i];
-    d.ws_t = wsf;
-    wsf += (3ll * d.H * d.Kw + 63) & ~63ll;
-    for (int y0 = 0; y0 < d.H; y0 += 16) rb.push_back(make_int2(i, y0));
-  }
-  const int64_t map_off = wsf;
-  const int64_t map_n = (int64_t)n_img * 3 * cfg->max_patch_h * cfg->max_patch_w;
-  wsf += map_n;
-  int rc;
-  float* ws;
-  if ((rc = oc.scratch(kWs, (size_t)wsf * 4, &ws))) return rc;
-  PlanBuf pb;
-  const size_t d_off = pb.add(D.data(), D.size());
-  const size_t rb_off = pb.add(rb.data(), rb.size());
-  const size_t lut_off = pb.add(B.img_lut, (size_t)B.n_rows * B.lut_w);
-  uint8_t* pd;
-  if ((rc = oc.upload(pb, &pd))) return rc;
-  const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
-  int32_t* map = (int32_t*)(ws + map_off);
-  HIPCHK(ctx, hipMemsetAsync(map, 0xFF, (size_t)map_n * 4, s));
-  const DecodeArgs a = decode_args(ctx, B, norm, lfq, codes.p, patches, (const int32_t*)(pd + lut_off), normed);
-  const float2* tw = ctx->fft_tab + fpl.tw_off;
-  const float4* pre = reinterpret_cast<const float4*>(ctx->fft_tab + fpl.ipre_off);
-  {
-    Timer t(ctx, s, "dec_map");
-    launch_dec_map((int64_t)B.n_rows * cfg->max_seq_len, dd, a, map, s);
-  }
-  {
-    Timer t(ctx, s, "idct_cols");
-    if (band)
-      launch_idct_cols512b(dd, n_img, ws, map, tw, pre, a, s, codes.type);
-    else
-      launch_idct_cols512(dd, n_img, D[0].qw, ws, map, tw, pre, a, s, codes.type);
-  }
-  {
-    Timer t(ctx, s, "idct_rows");
-    if (rows512)
-      launch_idct_rows512(band, dd, (const int2*)(pd + rb_off), (int)rb.size(), ws, rgb, px, tw, pre, ctx->cm, s);
-    else
-      launch_idct_rows_spec(1, dd, (const int2*)(pd + rb_off), (int)rb.size(), ws, rgb, px, tw, pre, ctx->cm, s);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  return 0;
-}
-
-// normed: patches are PatchNorm outputs (before inverse_norm); the FFT path
-// applies the inverse in its column kernel (the (c, strip) tables of a block
-// are image-independent), other geometries run dctae_norm_inverse's kernel
-// into the staging buffer first.  px: the pixel type of the caller's images
-// (B.out_off in pixels); the tag rides to the kernels that write them, every
-// workspace request, plan entry and launch before them is the same.  codes:
-// the caller's codes with their type, a tag that rides to the kernels that
-// load them (the column kernels of the FFT path, k_scatter_tokens) in the same way
-static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* norm, const dctae_lfq* lfq,
-                       const CodeSrc& codes, const float* patches, void* rgb, PixelType px, bool normed) {
+// The planner and launch sequence of every decode entry: token map -> spectrum
+// -> column DCT-III -> row DCT-III -> RGB, for a list of targets.  A plain
+// decode's targets are the batch's images (out at B.out_off); a frames call's
+// are its frames sorted by source image, one ImgDesc each with the source's
+// geometry and its own workspace and output offsets (dctae_frames.hip), which
+// the same kernels take as images: only the two token-driven kernels have a
+// frame form.  FFT path (every image 512 x 512): the column kernel expands
+// the tokens and, for PatchNorm-space patches (normed), inverts them; other
+// geometries scatter the tokens into Y for the GEMM pair, after
+// dctae_norm_inverse's kernel into the staging buffer.  px / codes.type: the
+// caller's pixel and code types, tags that ride to the kernels that write /
+// load them; every workspace request, plan entry and launch is the same.
+// clip to bytes ("staged"): the kernels write fp32 targets into the workspace
+// and k_clip_store writes the bytes.
+int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* norm, const dctae_lfq* lfq,
+                const CodeSrc& codes, const float* patches, void* out, PixelType px, bool normed,
+                const dctae_frames* fr, bool clip) {
   hipSetDevice(ctx->device);
   const dctae_fe_cfg* cfg = B.cfg;
   const hipStream_t s = B.s;
@@ -199,9 +139,10 @@ static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* n
   const char* own = nullptr;
   if (normed && (!norm || !norm->median_dev || !norm->b_dev || codes))
     own = "decode of PatchNorm-space patches needs the PatchNorm tables (and no codes)";
-  int rc = decode_check(ctx, B, own, rgb != nullptr, true);
+  int rc = decode_check(ctx, B, own, out != nullptr || (fr && fr->n_frames == 0), true);
   if (rc) return rc;
-  const int P = cfg->patch_size, PP = P * P, S = cfg->max_seq_len;
+  const int P = cfg->patch_size, PP = P * P;
+  const int64_t n_tok = (int64_t)n_rows * cfg->max_seq_len;
   if (codes) {
     if (!norm || !norm->median_dev || !norm->b_dev) return fail(ctx, DCTAE_EINVAL, "decode from codes needs PatchNorm");
     if ((rc = check_lfq(ctx, lfq, PP))) return rc;
@@ -209,33 +150,60 @@ static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* n
   } else if (n_rows > 0 && !patches) {
     return fail(ctx, DCTAE_EINVAL, "decode needs codes or patches");
   }
-  if (n_img == 0) return 0;
-  std::vector<ImgDesc> D;
-  int64_t wsf = 0, max_hw;
+  if (!fr && n_img == 0) return 0;
+  std::vector<ImgDesc> D, F;   // the batch's images; the frames sorted by image (stable)
+  int64_t max_hw;
   if ((rc = decode_geometry(ctx, B, D, &max_hw))) return rc;
-  for (ImgDesc& d : D) {   // the GEMM path's workspace: Y, U and the ipt image, image by image
-    d.ws_y = wsf;
-    wsf += 3ll * d.Kh * d.Kw;
-    d.ws_t = wsf;
-    wsf += 3ll * d.H * d.Kw;
-    d.ws_p = wsf;
-    wsf += 3ll * d.H * d.W;
+  std::vector<int> order;    // sorted frame g is the caller's frame order[g]
+  std::vector<int2> range;   // image im owns the sorted frames [range[im].x, range[im].y)
+  std::vector<int32_t> cut;
+  if (fr) {
+    if ((rc = frames_check(ctx, B, fr))) return rc;
+    if (fr->n_frames == 0) return 0;
+    if (!out) return fail(ctx, DCTAE_EINVAL, "bad decode descriptor");
+    for (int f = 0; f < fr->n_frames; ++f) order.push_back(f);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return fr->img[x] < fr->img[y]; });
+    range.assign(n_img, make_int2(0, 0));
+    max_hw = 1;
+    for (int g = 0; g < fr->n_frames; ++g) {
+      const int im = fr->img[order[g]];
+      if (g == 0 || fr->img[order[g - 1]] != im) range[im].x = g;
+      range[im].y = g + 1;
+      cut.push_back(fr->cut[order[g]]);
+      F.push_back(D[im]);
+      F[g].rgb_off = fr->out_off[order[g]];
+      max_hw = std::max<int64_t>(max_hw, (int64_t)D[im].H * D[im].W);
+    }
   }
-  // the GEMM path's slot map (k_dec_map: the later packed slot wins at a duplicate place, FE:639-643)
-  const int64_t gmap_off = (wsf + 63) & ~63ll;
-  const int64_t gmap_n = (int64_t)n_img * 3 * cfg->max_patch_h * cfg->max_patch_w;
-  // FFT path (dctae_idct.hip): every image 512 x 512 on the specialised plan, recommended LFQ
-  bool fftdec = ctx->opt.fft_decode && P == 14 && (!codes || (lfq->codebook_dim == 14 && lfq->num_codebooks == 14));
-  for (int i = 0; fftdec && i < n_img; ++i)
-    fftdec = D[i].H == 512 && D[i].W == 512 && D[i].qh <= 32 && D[i].qw == D[0].qw;
+  std::vector<ImgDesc>& T = fr ? F : D;   // the targets
+  const int n_tg = (int)T.size();
+  // where the kernels write a target: the caller's buffer, or fp32 staging in the workspace
+  const bool staged = clip && px == PixelType::kU8;
+  const PixelType wpx = staged ? PixelType::kF32 : px;
+
+  // The path (decode_path, dctae_dec_layout.h), then the specialised plan of its side.  Per image the predicate
+  // asks what the FFT kernels are compiled for, fftdec = D[i].H == 512 && D[i].W == 512 (kFftDecSide) at
+  // qh <= 32 and one qw; tests/test_pixel_loss_shapes_host.py reads the side out of this line for its cases
+  static_assert(kFftDecSide == 512, "the comment above quotes the side");
+  DecPath path = decode_path(ctx->opt, P, (bool)codes, codes ? lfq->codebook_dim : 0, codes ? lfq->num_codebooks : 0,
+                             D.data(), n_img);
   FftPlan fpl{};
-  if (fftdec) fftdec = fft_plan_for(ctx, 512, P, &fpl) == 0 && fpl.spec == 1;
+  if (path.fft && !(fft_plan_for(ctx, kFftDecSide, P, &fpl) == 0 && fpl.spec == 1)) path = DecPath{};
+  // k_idct_rows512 stores four byte pixels at once (dctae_u8_out.h): refused before any launch
+  for (int g = 0; wpx == PixelType::kU8 && path.rows512 && g < n_tg; ++g)
+    if (((uintptr_t)out + (uintptr_t)T[g].rgb_off) % 4) {
+      const std::string what = fr ? "frame" : "image";
+      return fail(ctx, DCTAE_EINVAL, what + " " + std::to_string(fr ? order[g] : g) + ": a 512 x 512 byte " + what +
+                  " on the 512-wide row kernel must start 4-byte aligned (" +
+                  (fr ? "out_dev + out_off[f])" : "rgb_dev + out_off[i])"));
+    }
+  const DecLayout L = decode_layout(T.data(), n_tg, path.fft, cfg->max_patch_h, cfg->max_patch_w, clip, staged);
+  std::vector<ClipSpan> cd;   // clip (frames only): from where the kernels wrote frame g to the caller's frame
+  for (int g = 0; clip && g < n_tg; ++g) cd.push_back({T[g].rgb_off, fr->out_off[order[g]], 3ll * T[g].H * T[g].W});
+
   OrderedCall oc(ctx, s);
-  if (fftdec)
-    return decode_fft(oc, B, D, fpl, norm, lfq, codes, patches, rgb, px, normed);
-  if (normed && n_rows > 0) {
-    // other geometries: the inverse over every packed token into the staging buffer, then as patches
-    const int64_t n_tok = (int64_t)n_rows * S;
+  if (!path.fft && normed && n_rows > 0) {
+    // PatchNorm-space patches on the GEMM path: inverted once over every packed token into the staging buffer
     float* inv;
     if ((rc = oc.scratch(kStage, (size_t)n_tok * PP * 4, &inv))) return rc;
     Timer t(ctx, s, "norm_inverse");
@@ -244,60 +212,92 @@ static int decode_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_norm* n
     patches = inv;
   }
   float* ws;
-  if ((rc = oc.scratch(kWs, (size_t)(gmap_off + gmap_n) * 4, &ws))) return rc;
+  if ((rc = oc.scratch(kWs, (size_t)L.total * 4, &ws))) return rc;
   std::vector<GemmProblem> probs;
   std::vector<TileRef> t1, t2;
-  for (const ImgDesc& d : D) {
+  for (int g = 0; !path.fft && g < n_tg; ++g) {
     GemmProblem g1, g2;
     const float *CW, *CH;
-    if ((rc = decode_gemm_pair(ctx, cfg, d, ws, &g1, &g2, &CW, &CH))) return rc;
-    int pr = (int)probs.size();
+    if ((rc = decode_gemm_pair(ctx, cfg, T[g], ws, &g1, &g2, &CW, &CH))) return rc;
+    add_tiles(t1, 2 * g, g1);
+    add_tiles(t2, 2 * g + 1, g2);
     probs.push_back(g1);
     probs.push_back(g2);
-    add_tiles(t1, pr, g1);
-    add_tiles(t2, pr + 1, g2);
   }
-  if (ctx->opt.xcd_order) {   // as the encode's GEMMs (xcd_deal_tiles): speed only
+  if (!path.fft && ctx->opt.xcd_order) {   // as the encode's GEMMs (xcd_deal_tiles): speed only
     xcd_deal_tiles(t1, probs.data(), 2);
     xcd_deal_tiles(t2, probs.data(), 1);
   }
+  // the plan: an empty list adds nothing, so a plain decode's carries no frame lists and each path only its own
   PlanBuf pb;
-  size_t d_off = pb.add(D.data(), D.size());
-  size_t g_off = pb.add(probs.data(), probs.size());
-  size_t t1_off = pb.add(t1.data(), t1.size());
-  size_t t2_off = pb.add(t2.data(), t2.size());
-  size_t lut_off = pb.add(B.img_lut, (size_t)n_rows * B.lut_w);
+  const PlanList<ImgDesc> pl_d = pb.add(D), pl_f = pb.add(F);
+  const PlanList<int2> pl_range = pb.add(range);
+  const PlanList<int32_t> pl_cut = pb.add(cut);
+  const PlanList<int2> pl_rb = pb.add(L.row_blocks);
+  const PlanList<GemmProblem> pl_g = pb.add(probs);
+  const PlanList<TileRef> pl_t1 = pb.add(t1), pl_t2 = pb.add(t2);
+  const PlanList<ClipSpan> pl_cd = pb.add(cd);
+  const size_t lut_off = pb.add(B.img_lut, (size_t)n_rows * B.lut_w);
   uint8_t* pd;
   if ((rc = oc.upload(pb, &pd))) return rc;
-  const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
-  HIPCHK(ctx, hipMemsetAsync(ws, 0, (size_t)wsf * 4, s));
-  // PatchNorm-space patches were inverted into the staging buffer above: plain patches here
-  const DecodeArgs a = decode_args(ctx, B, norm, lfq, codes.p, patches, (const int32_t*)(pd + lut_off), false);
-  int32_t* gmap = (int32_t*)(ws + gmap_off);
-  HIPCHK(ctx, hipMemsetAsync(gmap, 0xFF, (size_t)gmap_n * 4, s));
+  const ImgDesc* dd = pl_d.at(pd);
+  const ImgDesc* td = fr ? pl_f.at(pd) : dd;
+  int32_t* map = (int32_t*)(ws + L.map_off);
+  void* wout = staged ? (void*)ws : out;
+  if (!path.fft) HIPCHK(ctx, hipMemsetAsync(ws, 0, (size_t)L.wsf * 4, s));
+  // normed: the FFT path's column kernel inverts; the GEMM path's patches were inverted above
+  const DecodeArgs a = decode_args(ctx, B, norm, lfq, codes.p, patches, (const int32_t*)(pd + lut_off),
+                                   path.fft && normed);
+  HIPCHK(ctx, hipMemsetAsync(map, 0xFF, (size_t)L.map_n * 4, s));
   {
     Timer t(ctx, s, "dec_map");
-    launch_dec_map((int64_t)n_rows * S, dd, a, gmap, s);
+    if (fr)
+      launch_frames_map(n_tok, dd, a, pl_range.at(pd), pl_cut.at(pd), map, s);
+    else
+      launch_dec_map(n_tok, dd, a, map, s);
   }
-  {
-    Timer t(ctx, s, "scatter_tokens");
-    launch_scatter_tokens((int64_t)n_rows * S, dd, ws, a, gmap, s, codes.type);
-  }
-  {
-    Timer t(ctx, s, "idct_cols");
-    ctx_gemm(ctx, 3, (const GemmProblem*)(pd + g_off), (const TileRef*)(pd + t1_off), (int)t1.size(), s, 2);
-  }
-  {
+  if (path.fft) {
+    const float2* tw = ctx->fft_tab + fpl.tw_off;
+    const float4* pre = reinterpret_cast<const float4*>(ctx->fft_tab + fpl.ipre_off);
+    {
+      Timer t(ctx, s, "idct_cols");
+      if (path.band)
+        launch_idct_cols512b(td, n_tg, ws, map, tw, pre, a, s, codes.type);
+      else
+        launch_idct_cols512(td, n_tg, D[0].qw, ws, map, tw, pre, a, s, codes.type);
+    }
     Timer t(ctx, s, "idct_rows");
-    ctx_gemm(ctx, 3, (const GemmProblem*)(pd + g_off), (const TileRef*)(pd + t2_off), (int)t2.size(), s, 1);
-  }
-  {
+    if (path.rows512)
+      launch_idct_rows512(path.band, td, pl_rb.at(pd), pl_rb.n, ws, wout, wpx, tw, pre, ctx->cm, s);
+    else
+      launch_idct_rows_spec(1, td, pl_rb.at(pd), pl_rb.n, ws, wout, wpx, tw, pre, ctx->cm, s);
+  } else {
+    {
+      Timer t(ctx, s, "scatter_tokens");
+      if (fr)
+        launch_scatter_frames(n_tok, dd, td, ws, a, pl_range.at(pd), pl_cut.at(pd), map, s, codes.type);
+      else
+        launch_scatter_tokens(n_tok, dd, ws, a, map, s, codes.type);
+    }
+    {
+      Timer t(ctx, s, "idct_cols");
+      ctx_gemm(ctx, 3, pl_g.at(pd), pl_t1.at(pd), pl_t1.n, s, 2);
+    }
+    {
+      Timer t(ctx, s, "idct_rows");
+      ctx_gemm(ctx, 3, pl_g.at(pd), pl_t2.at(pd), pl_t2.n, s, 1);
+    }
     Timer t(ctx, s, "ipt_to_rgb");
-    launch_ipt_to_rgb(dd, n_img, max_hw, ws, rgb, px, ctx->cm, s);
+    launch_ipt_to_rgb(td, n_tg, max_hw, ws, wout, wpx, ctx->cm, s);
   }
+  if (clip && (rc = clip_launch(ctx, pl_cd.at(pd), n_tg, 3 * max_hw, (const float*)wout, (uint32_t*)(ws + L.mm_off),
+                                out, px, s)))
+    return rc;
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
+
+}  // namespace dctae
 
 extern "C" {
 
@@ -306,8 +306,8 @@ int dctae_decode(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, const 
                  const int64_t* ids, const uint8_t* key_pad, const int64_t* pos, const int64_t* ch,
                  const dctae_norm* norm, const dctae_lfq* lfq, const int64_t* codes, const float* patches,
                  float* rgb, void* stream) {
-  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
-                      (hipStream_t)stream};
+  const DecodeBatch B = decode_batch(cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos,
+                                     ch, stream);
   if (!ctx) return DCTAE_EINVAL;
   return decode_impl(ctx, B, norm, lfq, codes, patches, rgb, PixelType::kF32, false);
 }
@@ -317,8 +317,8 @@ int dctae_decode_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, con
                     const int64_t* ids, const uint8_t* key_pad, const int64_t* pos, const int64_t* ch,
                     const dctae_norm* norm, const dctae_lfq* lfq, const int64_t* codes, const float* patches,
                     uint8_t* rgb, void* stream) {
-  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
-                      (hipStream_t)stream};
+  const DecodeBatch B = decode_batch(cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos,
+                                     ch, stream);
   if (!ctx) return DCTAE_EINVAL;
   return decode_impl(ctx, B, norm, lfq, codes, patches, rgb, PixelType::kU8, false);
 }
@@ -328,8 +328,8 @@ int dctae_decode_normed(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows,
                         const int32_t* patch_hw, const int64_t* ids, const uint8_t* key_pad, const int64_t* pos,
                         const int64_t* ch, const dctae_norm* norm, const float* normed_patches, float* rgb,
                         void* stream) {
-  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
-                      (hipStream_t)stream};
+  const DecodeBatch B = decode_batch(cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos,
+                                     ch, stream);
   if (!ctx) return DCTAE_EINVAL;
   if (n_rows > 0 && !normed_patches) return fail(ctx, DCTAE_EINVAL, "decode needs the PatchNorm-space patches");
   return decode_impl(ctx, B, norm, nullptr, CodeSrc(), normed_patches, rgb, PixelType::kF32, true);
@@ -340,8 +340,8 @@ int dctae_decode_normed_u8(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_ro
                            const int32_t* patch_hw, const int64_t* ids, const uint8_t* key_pad, const int64_t* pos,
                            const int64_t* ch, const dctae_norm* norm, const float* normed_patches, uint8_t* rgb,
                            void* stream) {
-  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
-                      (hipStream_t)stream};
+  const DecodeBatch B = decode_batch(cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos,
+                                     ch, stream);
   if (!ctx) return DCTAE_EINVAL;
   if (n_rows > 0 && !normed_patches) return fail(ctx, DCTAE_EINVAL, "decode needs the PatchNorm-space patches");
   return decode_impl(ctx, B, norm, nullptr, CodeSrc(), normed_patches, rgb, PixelType::kU8, true);
@@ -353,8 +353,8 @@ int dctae_decode_c16(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows, co
                      const int64_t* ids, const uint8_t* key_pad, const int64_t* pos, const int64_t* ch,
                      const dctae_norm* norm, const dctae_lfq* lfq, const int16_t* codes, const float* patches,
                      float* rgb, void* stream) {
-  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
-                      (hipStream_t)stream};
+  const DecodeBatch B = decode_batch(cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos,
+                                     ch, stream);
   if (!ctx) return DCTAE_EINVAL;
   return decode_impl(ctx, B, norm, lfq, codes, patches, rgb, PixelType::kF32, false);
 }
@@ -364,8 +364,8 @@ int dctae_decode_u8_c16(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows,
                         const int32_t* patch_hw, const int64_t* ids, const uint8_t* key_pad, const int64_t* pos,
                         const int64_t* ch, const dctae_norm* norm, const dctae_lfq* lfq, const int16_t* codes,
                         const float* patches, uint8_t* rgb, void* stream) {
-  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos, ch,
-                      (hipStream_t)stream};
+  const DecodeBatch B = decode_batch(cfg, n_rows, img_lut, lut_w, n_img, out_hw, out_off, patch_hw, ids, key_pad, pos,
+                                     ch, stream);
   if (!ctx) return DCTAE_EINVAL;
   return decode_impl(ctx, B, norm, lfq, codes, patches, rgb, PixelType::kU8, false);
 }

@@ -25,6 +25,7 @@
 // is the precise one.  Nothing here uses floating-point atomics: the loss is
 // block partials (double) in the workspace, added in a fixed order by one block.
 #include "dctae_ctx.h"
+#include "dctae_dec_layout.h"
 #include "dctae_device.h"
 
 using namespace dctae;
@@ -329,28 +330,15 @@ int dctae_decode_backward(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_row
   const int64_t n_tok = (int64_t)n_rows * cfg->max_seq_len;
   if (n_tok > ((int64_t)1 << 31) - 1) return fail(ctx, DCTAE_EUNSUP, "decode backward: too many tokens in one call");
   std::vector<ImgDesc> D;
-  int64_t wsf = 0, max_hw;
+  int64_t max_hw;
   if ((rc = decode_geometry(ctx, B, D, &max_hw))) return rc;
-  // workspace: every Y first (one memset), then U / T and ipt / g_ipt per image,
-  // each on a 64-float boundary; then the slot map
-  for (ImgDesc& d : D) {
-    d.ws_y = wsf;
-    wsf += (3ll * d.Kh * d.Kw + 63) & ~63ll;
-  }
-  const int64_t y_floats = wsf;
-  for (ImgDesc& d : D) {
-    d.ws_t = wsf;
-    wsf += (3ll * d.H * d.Kw + 63) & ~63ll;
-    d.ws_p = wsf;
-    wsf += (3ll * d.H * d.W + 63) & ~63ll;
-  }
+  // workspace: every Y first (one memset), then U / T and ipt / g_ipt per image, the slot map, the DC coefficients
+  const DecBwdLayout L = decode_bwd_layout(D.data(), n_img, cfg->max_patch_h, cfg->max_patch_w);
   D.resize(std::max(n_img, 1));   // the plan holds a descriptor even without images
-  const int64_t gmap_off = wsf;
-  const int64_t gmap_n = (int64_t)n_img * 3 * cfg->max_patch_h * cfg->max_patch_w;
-  const int64_t dc_off = (gmap_off + gmap_n + 63) & ~63ll;   // the images' DC coefficients, 3 floats each
+  const int64_t y_floats = L.y_floats, gmap_off = L.map_off, gmap_n = L.map_n, dc_off = L.dc_off;
   OrderedCall oc(ctx, s);
   float* ws;
-  if ((rc = oc.scratch(kWs, std::max<size_t>((size_t)(dc_off + 3ll * n_img) * 4, 512), &ws))) return rc;
+  if ((rc = oc.scratch(kWs, L.request, &ws))) return rc;
   std::vector<GemmProblem> probs;
   std::vector<TileRef> t1, t2, t3, t4;
   for (int i = 0; i < n_img; ++i) {

@@ -39,8 +39,6 @@ inline int64_t chunk_estimate(const ImgDesc& d) {
   const Regions r = regions_of(d);
   return (r.t + 64 + (r.ipt ? r.ipt + 64 : 0) + (r.y ? r.y + 64 : 0)) * 4;
 }
-inline int64_t up64(int64_t v) { return (v + 63) & ~63ll; }   // 256-byte aligned regions (float4 strip loads)
-
 // ---- chunk cut and workspace layout ----
 struct JobRange {
   int i0, i1;         // images [i0, i1)

@@ -10,7 +10,9 @@
 // launch_ipt_to_rgb), which read tokens only through the map.  The GEMM path's
 // token scatter is the one kernel that is token-driven and so needs a frame
 // form (k_scatter_frames).  The frame tables travel in arguments of their own:
-// DecodeArgs, ImgDesc and every existing kernel are as they were.
+// DecodeArgs, ImgDesc and every existing kernel are as they were.  The planner
+// and the launch sequence are the decode's own (decode_impl, dctae_decode.hip),
+// which branches to the two launchers here where a frames call differs.
 #include "dctae_ctx.h"
 #include "dctae_device.h"
 #include "../../include/dctae_frames.h"
@@ -28,10 +30,11 @@ struct FrameTabs {
   const int32_t* cut;
 };
 
-// one image of dctae_image_clip / one clipped frame: n floats at in_off, n elements at out_off
+// one image of dctae_image_clip / one clipped frame as the kernels take it: ClipSpan's fields
 struct ClipDesc {
   int64_t in_off, out_off, n;
 };
+static_assert(sizeof(ClipDesc) == sizeof(ClipSpan) && alignof(ClipDesc) == alignof(ClipSpan), "clip_launch casts");
 
 // ---------------------------------------------------------------------------
 // slot map per frame: map[frame][c][w][h] = packed slot of the token (or -1),
@@ -90,13 +93,18 @@ __global__ void k_frames_map(int64_t n_tok, int64_t n4, const ImgDesc* __restric
     if (!a.key_pad[t]) frames_map_token(t, a.ids[t], a.ch[t], a.pos[2 * t], a.pos[2 * t + 1], imgs, a, ft, map);
 }
 
-void launch_frames_map(int64_t n_tok, const ImgDesc* imgs, const DecodeArgs& a, const FrameTabs& ft, int32_t* map,
-                       hipStream_t s) {
+}  // namespace
+
+void launch_frames_map(int64_t n_tok, const ImgDesc* imgs, const DecodeArgs& a, const int2* range, const int32_t* cut,
+                       int32_t* map, hipStream_t s) {
+  const FrameTabs ft{range, cut};
   const bool al = ((uintptr_t)a.ids | (uintptr_t)a.ch | (uintptr_t)a.pos) % 16 == 0 && (uintptr_t)a.key_pad % 4 == 0;
   const int64_t n4 = al ? n_tok / 4 : 0;
   const int gx = (int)std::min<int64_t>((std::max<int64_t>(n4, n_tok - 4 * n4) + 255) / 256, 8192);
   if (gx > 0) hipLaunchKernelGGL(k_frames_map, dim3(gx), dim3(256), 0, s, n_tok, n4, imgs, a, ft, map);
 }
+
+namespace {
 
 // ---------------------------------------------------------------------------
 // GEMM path: k_scatter_tokens for frames.  Token-driven like it (one element of
@@ -151,8 +159,11 @@ __global__ void k_scatter_frames(int64_t n_tok, const ImgDesc* __restrict__ imgs
   }
 }
 
+}  // namespace
+
 void launch_scatter_frames(int64_t n_tok, const ImgDesc* imgs, const ImgDesc* frames, float* ws, const DecodeArgs& a,
-                           const FrameTabs& ft, const int32_t* map, hipStream_t s, CodeType ct) {
+                           const int2* range, const int32_t* cut, const int32_t* map, hipStream_t s, CodeType ct) {
+  const FrameTabs ft{range, cut};
   const int64_t total = n_tok * a.P * a.P;
   const int gx = (int)std::min<int64_t>((total + 255) / 256, 16384);
   if (gx <= 0) return;
@@ -161,6 +172,8 @@ void launch_scatter_frames(int64_t n_tok, const ImgDesc* imgs, const ImgDesc* fr
   else
     hipLaunchKernelGGL(k_scatter_frames<int64_t>, dim3(gx), dim3(256), 0, s, n_tok, imgs, frames, ws, a, ft, map);
 }
+
+namespace {
 
 // ---------------------------------------------------------------------------
 // image_clip (util.py:143-147): y = (x - min) / (max - min) per image.
@@ -239,10 +252,13 @@ __global__ __launch_bounds__(256) void k_clip_store(const ClipDesc* __restrict__
   for (int64_t i = 4 * n4 + first; i < d.n; i += step) y[i] = store_px<Out>(__fdiv_rn(__fsub_rn(x[i], lo), span));
 }
 
+}  // namespace
+
 // descs / mm on the device; mm is cleared here.  fp32 results may overwrite their inputs.
 // Two timed stages: clip_minmax, clip_store
-int clip_launch(dctae_ctx* ctx, const ClipDesc* descs, int n, int64_t max_n, const float* in, uint32_t* mm, void* out,
+int clip_launch(dctae_ctx* ctx, const ClipSpan* spans, int n, int64_t max_n, const float* in, uint32_t* mm, void* out,
                 PixelType px, hipStream_t s) {
+  const ClipDesc* descs = reinterpret_cast<const ClipDesc*>(spans);
   HIPCHK(ctx, hipMemsetAsync(mm, 0, (size_t)n * 8, s));
   // k_clip_store: two values' worth of 16-byte steps per thread; k_clip_minmax: eight, so that few blocks
   // of an image meet at its two words (one block per 2048 values ran at 0.18 TB/s, bound by the atomics)
@@ -280,216 +296,6 @@ int frames_check(dctae_ctx* ctx, const DecodeBatch& B, const dctae_frames* fr) {
   return 0;
 }
 
-// The planner: decode_impl's checks, geometry and path choice for the batch,
-// then everything per frame.  out / px: the caller's frames and their type;
-// with clip and bytes the kernels write fp32 frames into the workspace and
-// k_clip_store writes the bytes.
-int decode_frames_impl(dctae_ctx* ctx, const DecodeBatch& B, const dctae_frames* fr, const dctae_norm* norm,
-                       const dctae_lfq* lfq, const CodeSrc& codes, const float* patches, bool normed, bool clip,
-                       void* out, PixelType px) {
-  hipSetDevice(ctx->device);
-  const dctae_fe_cfg* cfg = B.cfg;
-  const hipStream_t s = B.s;
-  const int n_rows = B.n_rows, n_img = B.n_img;
-  const char* own = nullptr;
-  if (normed && (!norm || !norm->median_dev || !norm->b_dev || codes))
-    own = "decode of PatchNorm-space patches needs the PatchNorm tables (and no codes)";
-  int rc = decode_check(ctx, B, own, out != nullptr || fr->n_frames == 0, true);
-  if (rc) return rc;
-  const int P = cfg->patch_size, PP = P * P, S = cfg->max_seq_len;
-  if (codes) {
-    if (!norm || !norm->median_dev || !norm->b_dev) return fail(ctx, DCTAE_EINVAL, "decode from codes needs PatchNorm");
-    if ((rc = check_lfq(ctx, lfq, PP))) return rc;
-    if (codes.type == CodeType::kI16 && (rc = check_codes16(ctx, lfq))) return rc;
-  } else if (n_rows > 0 && !patches) {
-    return fail(ctx, DCTAE_EINVAL, "decode needs codes or patches");
-  }
-  std::vector<ImgDesc> D;   // the batch's images: geometry only
-  int64_t max_hw_all;
-  if ((rc = decode_geometry(ctx, B, D, &max_hw_all))) return rc;
-  if ((rc = frames_check(ctx, B, fr))) return rc;
-  const int n_fr = fr->n_frames;
-  if (n_fr == 0) return 0;
-  if (!out) return fail(ctx, DCTAE_EINVAL, "bad decode descriptor");
-
-  // frames sorted by image (stable): sorted frame g is the caller's frame order[g]
-  std::vector<int> order(n_fr);
-  for (int f = 0; f < n_fr; ++f) order[f] = f;
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return fr->img[x] < fr->img[y]; });
-  std::vector<int2> range(n_img, make_int2(0, 0));
-  std::vector<int32_t> cut(n_fr);
-  std::vector<ImgDesc> F(n_fr);
-  int64_t max_hw = 1;
-  for (int g = 0; g < n_fr; ++g) {
-    const int im = fr->img[order[g]];
-    if (g == 0 || fr->img[order[g - 1]] != im) range[im].x = g;
-    range[im].y = g + 1;
-    cut[g] = fr->cut[order[g]];
-    F[g] = D[im];
-    max_hw = std::max<int64_t>(max_hw, (int64_t)D[im].H * D[im].W);
-  }
-  // where the kernels write frame g: the caller's buffer, or fp32 staging in the workspace (clip to bytes)
-  const bool staged = clip && px == PixelType::kU8;
-  const PixelType wpx = staged ? PixelType::kF32 : px;
-
-  // the path of dctae_decode for this batch (decode_impl)
-  bool fftdec = ctx->opt.fft_decode && P == 14 && (!codes || (lfq->codebook_dim == 14 && lfq->num_codebooks == 14));
-  for (int i = 0; fftdec && i < n_img; ++i)
-    fftdec = D[i].H == 512 && D[i].W == 512 && D[i].qh <= 32 && D[i].qw == D[0].qw;
-  FftPlan fpl{};
-  if (fftdec) fftdec = fft_plan_for(ctx, 512, P, &fpl) == 0 && fpl.spec == 1;
-  const bool rows512 = fftdec && ctx->opt.dec_rows_kernel == 3 && D[0].qw == 32;
-  const bool band = rows512 && ctx->opt.dec_cols_kernel == 2;
-  for (int g = 0; wpx == PixelType::kU8 && rows512 && g < n_fr; ++g)
-    if (((uintptr_t)out + (uintptr_t)fr->out_off[order[g]]) % 4)
-      return fail(ctx, DCTAE_EINVAL, "frame " + std::to_string(order[g]) + ": a 512 x 512 byte frame on the 512-wide "
-                  "row kernel must start 4-byte aligned (out_dev + out_off[f])");
-
-  // workspace, frame by frame as the forward lays it out image by image
-  int64_t wsf = 0;
-  std::vector<int2> rb;
-  for (int g = 0; g < n_fr; ++g) {
-    ImgDesc& d = F[g];
-    if (fftdec) {
-      d.ws_t = wsf;
-      wsf += (3ll * d.H * d.Kw + 63) & ~63ll;
-      for (int y0 = 0; y0 < d.H; y0 += 16) rb.push_back(make_int2(g, y0));
-    } else {
-      d.ws_y = wsf;
-      wsf += 3ll * d.Kh * d.Kw;
-      d.ws_t = wsf;
-      wsf += 3ll * d.H * d.Kw;
-      d.ws_p = wsf;
-      wsf += 3ll * d.H * d.W;
-    }
-  }
-  const int64_t map_off = (wsf + 63) & ~63ll;
-  const int64_t map_n = (int64_t)n_fr * 3 * cfg->max_patch_h * cfg->max_patch_w;
-  int64_t end = map_off + map_n;
-  const int64_t mm_off = (end + 63) & ~63ll;   // two words per frame
-  if (clip) end = mm_off + 2ll * n_fr;
-  std::vector<ClipDesc> cd;
-  for (int g = 0; g < n_fr; ++g) {
-    ImgDesc& d = F[g];
-    const int64_t n = 3ll * d.H * d.W, off = fr->out_off[order[g]];
-    d.rgb_off = off;
-    if (staged) {
-      end = (end + 63) & ~63ll;
-      d.rgb_off = end;
-      end += n;
-    }
-    if (clip) cd.push_back({d.rgb_off, off, n});
-  }
-
-  OrderedCall oc(ctx, s);
-  if (!fftdec && normed && n_rows > 0) {
-    // PatchNorm-space patches on the GEMM path: inverted once into the staging buffer, shared by the frames
-    const int64_t n_tok = (int64_t)n_rows * S;
-    float* inv;
-    if ((rc = oc.scratch(kStage, (size_t)n_tok * PP * 4, &inv))) return rc;
-    Timer t(ctx, s, "norm_inverse");
-    launch_norm(patches, B.ch, B.pos, n_tok, PP, cfg->max_patch_h, cfg->max_patch_w, norm->median_dev, norm->b_dev,
-                norm->eps, norm->min_val, norm->max_val, 1, inv, ctx->err_dev, s);
-    patches = inv;
-  }
-  float* ws;
-  if ((rc = oc.scratch(kWs, (size_t)end * 4, &ws))) return rc;
-  std::vector<GemmProblem> probs;
-  std::vector<TileRef> t1, t2;
-  if (!fftdec) {
-    for (const ImgDesc& d : F) {
-      GemmProblem g1, g2;
-      const float *CW, *CH;
-      if ((rc = decode_gemm_pair(ctx, cfg, d, ws, &g1, &g2, &CW, &CH))) return rc;
-      const int pr = (int)probs.size();
-      probs.push_back(g1);
-      probs.push_back(g2);
-      add_tiles(t1, pr, g1);
-      add_tiles(t2, pr + 1, g2);
-    }
-    if (ctx->opt.xcd_order) {
-      xcd_deal_tiles(t1, probs.data(), 2);
-      xcd_deal_tiles(t2, probs.data(), 1);
-    }
-  }
-  PlanBuf pb;
-  const size_t d_off = pb.add(D.data(), D.size());
-  const size_t f_off = pb.add(F.data(), F.size());
-  const size_t r_off = pb.add(range.data(), range.size());
-  const size_t c_off = pb.add(cut.data(), cut.size());
-  const size_t rb_off = pb.add(rb.data(), rb.size());
-  const size_t g_off = pb.add(probs.data(), probs.size());
-  const size_t t1_off = pb.add(t1.data(), t1.size());
-  const size_t t2_off = pb.add(t2.data(), t2.size());
-  const size_t cd_off = pb.add(cd.data(), cd.size());
-  const size_t lut_off = pb.add(B.img_lut, (size_t)n_rows * B.lut_w);
-  uint8_t* pd;
-  if ((rc = oc.upload(pb, &pd))) return rc;
-  const ImgDesc* dd = (const ImgDesc*)(pd + d_off);
-  const ImgDesc* fd = (const ImgDesc*)(pd + f_off);
-  const FrameTabs ft{(const int2*)(pd + r_off), (const int32_t*)(pd + c_off)};
-  int32_t* map = (int32_t*)(ws + map_off);
-  void* wout = staged ? (void*)ws : out;
-  const int64_t n_tok = (int64_t)n_rows * S;
-  HIPCHK(ctx, hipMemsetAsync(map, 0xFF, (size_t)map_n * 4, s));
-  if (fftdec) {
-    const DecodeArgs a = decode_args(ctx, B, norm, lfq, codes.p, patches, (const int32_t*)(pd + lut_off), normed);
-    const float2* tw = ctx->fft_tab + fpl.tw_off;
-    const float4* pre = reinterpret_cast<const float4*>(ctx->fft_tab + fpl.ipre_off);
-    {
-      Timer t(ctx, s, "dec_map");
-      launch_frames_map(n_tok, dd, a, ft, map, s);
-    }
-    {
-      Timer t(ctx, s, "idct_cols");
-      if (band)
-        launch_idct_cols512b(fd, n_fr, ws, map, tw, pre, a, s, codes.type);
-      else
-        launch_idct_cols512(fd, n_fr, D[0].qw, ws, map, tw, pre, a, s, codes.type);
-    }
-    {
-      Timer t(ctx, s, "idct_rows");
-      if (rows512)
-        launch_idct_rows512(band, fd, (const int2*)(pd + rb_off), (int)rb.size(), ws, wout, wpx, tw, pre, ctx->cm, s);
-      else
-        launch_idct_rows_spec(1, fd, (const int2*)(pd + rb_off), (int)rb.size(), ws, wout, wpx, tw, pre, ctx->cm, s);
-    }
-  } else {
-    HIPCHK(ctx, hipMemsetAsync(ws, 0, (size_t)wsf * 4, s));
-    // PatchNorm-space patches were inverted into the staging buffer above: plain patches here
-    const DecodeArgs a = decode_args(ctx, B, norm, lfq, codes.p, patches, (const int32_t*)(pd + lut_off), false);
-    {
-      Timer t(ctx, s, "dec_map");
-      launch_frames_map(n_tok, dd, a, ft, map, s);
-    }
-    {
-      Timer t(ctx, s, "scatter_tokens");
-      launch_scatter_frames(n_tok, dd, fd, ws, a, ft, map, s, codes.type);
-    }
-    {
-      Timer t(ctx, s, "idct_cols");
-      ctx_gemm(ctx, 3, (const GemmProblem*)(pd + g_off), (const TileRef*)(pd + t1_off), (int)t1.size(), s, 2);
-    }
-    {
-      Timer t(ctx, s, "idct_rows");
-      ctx_gemm(ctx, 3, (const GemmProblem*)(pd + g_off), (const TileRef*)(pd + t2_off), (int)t2.size(), s, 1);
-    }
-    {
-      Timer t(ctx, s, "ipt_to_rgb");
-      launch_ipt_to_rgb(fd, n_fr, max_hw, ws, wout, wpx, ctx->cm, s);
-    }
-  }
-  if (clip) {
-    if ((rc = clip_launch(ctx, (const ClipDesc*)(pd + cd_off), n_fr, 3 * max_hw, (const float*)wout,
-                          (uint32_t*)(ws + mm_off), out, px, s)))
-      return rc;
-  }
-  HIPCHK(ctx, hipGetLastError());
-  return 0;
-}
-
-}  // namespace
-
 }  // namespace dctae
 
 extern "C" {
@@ -511,13 +317,13 @@ int dctae_decode_frames(dctae_ctx* ctx, const dctae_fe_cfg* cfg, int32_t n_rows,
   if (normed != 0 && normed != 1) return fail(ctx, DCTAE_EINVAL, "normed: 0 or 1, got " + std::to_string(normed));
   // the batch's images have no offsets of their own here: the frames carry them
   const std::vector<int64_t> zero((size_t)std::max(n_img, 1), 0);
-  const DecodeBatch B{cfg, n_rows, img_lut, lut_w, n_img, out_hw, zero.data(), patch_hw, ids, key_pad, pos, ch,
-                      (hipStream_t)stream};
+  const DecodeBatch B = decode_batch(cfg, n_rows, img_lut, lut_w, n_img, out_hw, zero.data(), patch_hw, ids, key_pad,
+                                     pos, ch, stream);
   CodeSrc cs;
   if (codes) cs = codes_type == DCTAE_CODES_I16 ? CodeSrc((const int16_t*)codes) : CodeSrc((const int64_t*)codes);
   if (normed && n_rows > 0 && !patches) return fail(ctx, DCTAE_EINVAL, "decode needs the PatchNorm-space patches");
-  return decode_frames_impl(ctx, B, frames, norm, lfq, cs, patches, normed != 0, clip == DCTAE_CLIP_MINMAX, out,
-                            out_type == DCTAE_PIXEL_U8 ? PixelType::kU8 : PixelType::kF32);
+  return decode_impl(ctx, B, norm, lfq, cs, patches, out, out_type == DCTAE_PIXEL_U8 ? PixelType::kU8 : PixelType::kF32,
+                     normed != 0, frames, clip == DCTAE_CLIP_MINMAX);
 }
 
 int dctae_image_clip(dctae_ctx* ctx, int32_t n_img, const int32_t* hw, const int64_t* in_off, const float* in,
@@ -529,7 +335,7 @@ int dctae_image_clip(dctae_ctx* ctx, int32_t n_img, const int32_t* hw, const int
     return fail(ctx, DCTAE_EINVAL, "image_clip: n_img outside [0, 65535], got " + std::to_string(n_img));
   if (n_img > 0 && (!hw || !in_off || !out_off || !in || !out))
     return fail(ctx, DCTAE_EINVAL, "image_clip: NULL array or buffer");
-  std::vector<ClipDesc> cd((size_t)n_img);
+  std::vector<ClipSpan> cd((size_t)n_img);
   int64_t max_n = 1;
   for (int i = 0; i < n_img; ++i) {
     if (hw[2 * i] < 1 || hw[2 * i + 1] < 1)
@@ -550,7 +356,7 @@ int dctae_image_clip(dctae_ctx* ctx, int32_t n_img, const int32_t* hw, const int
   const size_t cd_off = pb.add(cd.data(), cd.size());
   uint8_t* pd;
   if ((rc = oc.upload(pb, &pd))) return rc;
-  if ((rc = clip_launch(ctx, (const ClipDesc*)(pd + cd_off), n_img, max_n, in, mm, out,
+  if ((rc = clip_launch(ctx, (const ClipSpan*)(pd + cd_off), n_img, max_n, in, mm, out,
                         out_type == DCTAE_PIXEL_U8 ? PixelType::kU8 : PixelType::kF32, s)))
     return rc;
   HIPCHK(ctx, hipGetLastError());

@@ -62,6 +62,9 @@ __host__ __device__ inline int stage_pos(const ImgDesc& d, int f) {
   return ((c << 5) + w) * 32 + h;
 }
 
+// workspace regions start on 64 floats (256 bytes: float4 strip loads), dctae_enc_layout.h / dctae_dec_layout.h
+inline int64_t up64(int64_t v) { return (v + 63) & ~63ll; }
+
 // Generic batched strided fp32 GEMM problem:
 //   O[c][m][n] = sum_k A[c][m][k] * B[c][n][k]     (c < C)
 struct GemmProblem {

@@ -170,11 +170,23 @@ void launch_idct_cols512(const ImgDesc* imgs, int n_img, int qw, float* ws, cons
 void launch_idct_rows_spec(int spec, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, void* rgb,
                            PixelType px, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s);
 
-// px = kU8: four pixels per store, every image's base 4-byte aligned (decode_fft refuses otherwise)
+// px = kU8: four pixels per store, every image's base 4-byte aligned (decode_impl refuses otherwise)
 void launch_idct_rows512(bool band, const ImgDesc* imgs, const int2* blocks, int n_blocks, const float* ws, void* rgb,
                          PixelType px, const float2* tw, const float4* pre, const ColorMats& cm, hipStream_t s);
 void launch_rows512(const ImgDesc* imgs, const int2* blocks, int n_blocks, const void* rgb, PixelType px, float* ws,
                     const float2* tw, const float2* post, const ColorMats& cm, hipStream_t s);
+
+// progressive decode (dctae_frames.hip): the two token-driven kernels in their frame form.  range / cut: image im
+// owns the sorted frames [range[im].x, range[im].y), sorted frame g cuts its image's row at cut[g];
+// frames: one descriptor per sorted frame
+void launch_frames_map(int64_t n_tok, const ImgDesc* imgs, const DecodeArgs& a, const int2* range, const int32_t* cut,
+                       int32_t* map, hipStream_t s);
+void launch_scatter_frames(int64_t n_tok, const ImgDesc* imgs, const ImgDesc* frames, float* ws, const DecodeArgs& a,
+                           const int2* range, const int32_t* cut, const int32_t* map, hipStream_t s, CodeType ct);
+// one image of clip_launch (dctae_ctx.h): n floats at in_off, n elements at out_off
+struct ClipSpan {
+  int64_t in_off, out_off, n;
+};
 
 int cols7_grid(int n_list, int qw, int ipb);
 // band-layout column pass of 512 x 512 images (k_cols512b; the rows wrote T' with band = 1)

@@ -92,9 +92,10 @@ def test_every_entry_has_its_twins_row_and_call_body():
         assert shared in body and shared in _closure(funcs, twin), (k, shared)
         assert re.search(SCOPE, _closure(funcs, shared)), f"{shared}: the OrderedCall is opened in the shared body"
         assert ("err_dev" in res) == ("err_dev" in body), k
-    # the decode entries call decode_impl themselves, as their twins do
+    # the decode entries call decode_impl themselves, as their twins and the frames entry do
     for k in ("dctae_decode_c16", "dctae_decode_u8_c16"):
         assert "decode_impl" in funcs[k] and "decode_impl" in funcs[TWINS[k][0]]
+    assert "decode_impl" in funcs["dctae_decode_frames"]
 
 
 def test_the_existing_headers_are_untouched():

@@ -108,7 +108,7 @@ def test_scratch_only_inside_an_ordered_call():
     # nothing in the unit names the context's buffers directly
     assert not re.search(r"ctx->(?:scratch|plan\b|plan_host|plan_last)", unit)
     funcs = _bodies()
-    for name in ("decode_frames_impl", "dctae_image_clip"):   # the scope opens before the first use
+    for name in ("decode_impl", "dctae_image_clip"):   # the scope opens before the first use
         body = funcs[name]
         assert re.search(SCOPE, body).start() < re.search(SCRATCH, body).start(), name
     assert "dctae_frames.hip" in open(os.path.join(CSRC, "Makefile")).read()

@@ -61,6 +61,7 @@ def test_sources_agree_with_the_table():
             assert uses and ordered, f"{k}: a decode entry outside the OrderedCall scope"
             # the same planner and launch sequence as the fp32 entry: one shared call body, hence the twin's row
             assert "decode_impl" in funcs[k] and "decode_impl" in funcs[twin]
+            assert "decode_impl" in funcs["dctae_decode_frames"]   # the frames entry shares it too
             assert (res, how) == TABLE[twin][:2], k
         else:
             assert how == NONE and not res and why
